@@ -14,11 +14,21 @@ root finished on every rank (reth_amd/sharding.py). scaling="strong": the
 TOTAL job (one root over the same 10M x 64 state) is fixed as ranks grow;
 the driver computes efficiency from the per-N values.
 
-CPU baseline: the C oracle (reth-algorithm restatement), one thread per host
-core, timed on the ACTUAL full-shape state (the same device-generated
-entries, copied to host; oracle root asserted equal to the GPU root) —
-measured, not extrapolated. The single-thread figure is sample-scaled and
-labeled as such. Both are reported baselines, not the optimisation target.
+A plain run (no --full) does only what the headline figure needs: setup,
+warmup, the timed steps, the optional --dump-outputs, and the result line
+(the roofline / engine_stats fields come for free from the last timed step).
+
+CPU baseline (--full only): the C oracle (reth-algorithm restatement), one
+thread per host core, timed on the ACTUAL full-shape state (the same
+device-generated entries, copied to host; oracle root asserted equal to the
+GPU root) — measured, not extrapolated. The single-thread figure is
+sample-scaled and labeled as such. Both are reported baselines, not the
+optimisation target; without --full both fields are null.
+
+--dump-outputs DIR writes what the last timed step returned to its caller —
+the 32-byte state root — as DIR/root.npy (float32, one element per byte).
+The inputs are a pure function of the arguments (seeded generator), so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -48,9 +58,17 @@ def main():
     ap.add_argument("--accounts", type=int, default=10_000_000)
     ap.add_argument("--slots", type=int, default=64)
     ap.add_argument("--cpu-sample-accounts", type=int, default=60_000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: "
+                         "the CPU baselines (see --cpu-baseline) and the "
+                         "full-shape oracle-root == GPU-root comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned (the state root) to DIR/root.npy")
     ap.add_argument("--cpu-baseline", choices=["full", "sample", "off"],
                     default="full",
-                    help="full: run the threaded C oracle on the ACTUAL "
+                    help="with --full only. "
+                         "full: run the threaded C oracle on the ACTUAL "
                          "full-shape state (D2H of the same device-generated "
                          "entries; ~3 min at 10M x 64, root checked against "
                          "the GPU result); sample: bounded sample scaled "
@@ -71,6 +89,8 @@ def main():
                          "base, plus per-step storage delta rows "
                          "(0 = the configs[4] accounts-only shape)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.incremental:
         args.slots = args.incremental_slots  # configs[4] default: accounts-only
 
@@ -240,6 +260,13 @@ def main():
     ms_per_step = elapsed * 1000.0 / args.steps
     stats = eng.stats()
 
+    # ---- --dump-outputs: what the last timed step handed its caller ----
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "root.npy"),
+                np.frombuffer(root, dtype=np.uint8).astype(np.float32))
+
     # optional property check (untimed): sharded composition equals root
     if args.check and world == 1:
         refs, lens, roots_, counts = eng.subtree_roots()
@@ -264,14 +291,16 @@ def main():
     hash_blocks = stats["leaf_blocks"] + stats["branch_blocks"]
     hash_s = (stats["leaf_hash_ms"] + stats["branch_hash_ms"]) / 1000.0
 
-    # ---- CPU baseline: the C-oracle restatement of reth's algorithm
-    # (kind "port"), one thread per host core (okc_state_root_par).
+    # ---- CPU baseline (--full only): the C-oracle restatement of reth's
+    # algorithm (kind "port"), one thread per host core (okc_state_root_par).
     # Default ("full", non-incremental runs): the ACTUAL full-shape state —
     # the same device-generated entries copied D2H — measured unscaled,
     # with the oracle root asserted equal to the GPU root (a full-scale
     # parity pin for free). The single-thread leg stays sampled+scaled
     # (a full 1-core run is ~33 min) and is labeled as such.
-    cpu_mode = "off" if args.no_cpu_baseline else args.cpu_baseline
+    cpu_mode = args.cpu_baseline if args.full else "off"
+    if args.no_cpu_baseline:
+        cpu_mode = "off"
     if args.incremental and cpu_mode == "full":
         cpu_mode = "sample"  # the incremental step has no full-shape CPU twin
     cpu_baseline = None
