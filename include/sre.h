@@ -323,6 +323,19 @@ int sre_get_stats(sre_ctx *ctx, sre_stats *out);
 /* Last error string for ctx (or the global creation error when ctx==NULL). */
 const char *sre_last_error(const sre_ctx *ctx);
 
+/* Read-only: which branch-pipeline paths the last root-type call took
+ * (sre_root, sre_storage_roots, sre_subtree_roots, sre_root_retaining,
+ * sre_incremental_root, sre_root_from_nodes, the *_with_updates forms and
+ * both proof calls reset the counters on entry; they sum over the storage
+ * and account passes):
+ *   out[0] levels that used the branch-size class partition
+ *   out[1] groups hashed by the fused one-block kernel
+ *   out[2] branch-pipeline chunks launched
+ *   out[3] levels that ran the two-stream ping-pong (more than one chunk)
+ * Exists so tests that lower the size gates (SRE_CLS_MIN, SRE_BR_CHUNK —
+ * see DESIGN.md) can prove the gated path actually ran. */
+int sre_get_path_counters(sre_ctx *ctx, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,8 @@ Pinned against consensus data: the genesis stateRoot vectors in
 /root/reference/crates/trie/db/tests/trie.rs:420-519.
 """
 
+import contextlib
+
 # --------------------------------------------------------------------------
 # Keccak-256 (original Keccak padding 0x01, NOT FIPS-202 SHA3's 0x06).
 # Independent of the C oracle's implementation.
@@ -227,6 +229,73 @@ def state_root(accounts: dict) -> bytes:
         sr = storage_root(slots)
         items[k] = account_value(nonce, balance, sr, code_hash)
     return trie_root(items)
+
+
+def iter_nodes(items, pos=0):
+    """Yield (depth, kind, nmem, rlp) for every node of the trie
+    `_build(items, pos)` builds, parents first — kind is "leaf", "ext" or
+    "branch", depth the nibble position the node starts at, nmem a
+    branch's child count (0 otherwise). Inline (< 32 B) nodes are yielded
+    too. Lets tests assert that a crafted trie really contains a node of a
+    given RLP length. Quadratic in depth (every node is rebuilt from its
+    items): small tries only."""
+    rlp = _build(items, pos)
+    if len(items) == 1:
+        yield pos, "leaf", 0, rlp
+        return
+    first, last = items[0][0], items[-1][0]
+    p = pos
+    while p < len(first) and p < len(last) and first[p] == last[p]:
+        p += 1
+    if p > pos:
+        yield pos, "ext", 0, rlp
+        yield from iter_nodes(items, p)
+        return
+    kids = []
+    i = 0
+    for nib in range(16):
+        j = i
+        while j < len(items) and items[j][0][pos] == nib:
+            j += 1
+        if j > i:
+            kids.append(items[i:j])
+            i = j
+    yield pos, "branch", len(kids), rlp
+    for kid in kids:
+        yield from iter_nodes(kid, pos + 1)
+
+
+def storage_nodes(slots: dict):
+    """iter_nodes over the storage trie of {hashed_slot: int_value}."""
+    items = sorted((nibbles_of(k), rlp_int(v)) for k, v in slots.items()
+                   if v != 0)
+    if items:
+        yield from iter_nodes(items, 0)
+
+
+@contextlib.contextmanager
+def accelerated(keccak):
+    """Test-speed mode for walking MANY proofs over one large item list:
+    inside the block the keccak primitive is `keccak` (the caller passes
+    one that is itself pinned against keccak256 above) and `_build` is
+    memoized per (first key, item count, depth) — which names a slice of
+    one sorted item list uniquely, so use a single trie per block. The
+    trie logic that runs is still the code in this module."""
+    global keccak256, _build
+    saved = keccak256, _build
+    plain, memo = _build, {}
+
+    def cached(items, pos):
+        k = (items[0][0], len(items), pos)
+        if k not in memo:
+            memo[k] = plain(items, pos)
+        return memo[k]
+
+    keccak256, _build = keccak, cached
+    try:
+        yield
+    finally:
+        keccak256, _build = saved
 
 
 def _collect_proof(items, pos, target, is_root, nodes):

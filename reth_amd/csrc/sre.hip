@@ -1241,10 +1241,15 @@ struct byte_appender {
         pos = total & 7;
         cur &= pos ? (1ull << (8 * pos)) - 1 : 0;
     }
-    // finish the message: flush, zero-fill to the last word of block nb,
-    // and set the keccak pad end bit (0x80 in the final byte).
+    // finish the message with the keccak pad10*1: the start byte 0x01
+    // right after the message, zero-fill to the last word of block nb, and
+    // the end bit (0x80) in the block's final byte. The start byte goes
+    // into `cur` WITHOUT the flush put() would do: when the message ends
+    // one byte short of the rate (len % 136 == 135) both pad bytes are the
+    // same byte, and a flushed final word would be overwritten below.
     __device__ __forceinline__ void finish(int nb)
     {
+        cur |= (uint64_t)0x01 << (8 * pos);
         int last = nb * 17 - 1;
         while (widx < last) {
             *slot64(widx) = cur;
@@ -1427,8 +1432,7 @@ __global__ void __launch_bounds__(BLOCK_A) k_branch_assemble(
         }
         ap.put(0x80); // empty value item
     }
-    ap.put(0x01); // keccak pad start
-    ap.finish(nb);
+    ap.finish(nb); // keccak pad
     mt.br_len = (uint16_t)br_len;
     meta[g] = mt;
 }
@@ -1792,8 +1796,7 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
                     ap.put(0x80);
                 ap.put(0x80); // empty value item
             }
-            ap.put(0x01); // keccak pad start
-            ap.finish(1);
+            ap.finish(1); // keccak pad
             uint64_t s[25];
 #pragma unroll
             for (int i = 0; i < 17; ++i)
@@ -3092,6 +3095,11 @@ struct sre_ctx {
     // per delta at the 200M-account config)
     size_t acct_pool_bytes = 0, st_pool_bytes = 0;
     sre_stats stats{};
+    // branch-pipeline path counters (sre_get_path_counters): [0] levels that
+    // used the class partition, [1] groups sent to k_branch_fused1,
+    // [2] chunks launched, [3] levels that ran the two-stream ping-pong.
+    // Reset at the start of every root-type call.
+    uint64_t path_cnt[4] = {0, 0, 0, 0};
     // TrieUpdates retention (sre_root_with_updates)
     bool retain_updates = false;
     std::vector<sre_update_row> updates;
@@ -3460,6 +3468,26 @@ struct pass_out {
 
 static int check_err(sre_ctx *ctx, uint32_t *d_err);
 
+// Test gates for the size-gated branch pipeline (read per call; unset =
+// production values). SRE_CLS_MIN: minimum groups per level for the class
+// partition (and therefore the fused kernel) — below the default the win is
+// noise. SRE_BR_CHUNK: branch-pipeline chunk in GROUPS (floor 256); tests
+// lower both so small states run the chunked two-stream path.
+static uint64_t cls_min_groups()
+{
+    const char *e = getenv("SRE_CLS_MIN");
+    return e ? (uint64_t)atoll(e) : (1ull << 14);
+}
+
+static uint64_t br_chunk_groups()
+{
+    const char *e = getenv("SRE_BR_CHUNK");
+    if (!e)
+        return (uint64_t)(SRE_BR_CHUNK_MB) << 20;
+    long long v = atoll(e);
+    return v < 256 ? 256 : (uint64_t)v;
+}
+
 // updates_kind: -1 = off; 0/1 = retain TrieUpdates rows of this trie kind
 // (d_bhash then holds 32 B per underlying entry for branch-hash lookups).
 static int run_levels(sre_ctx *ctx, uint64_t n, node_rec *d_recs, uint8_t *d_depths,
@@ -3661,8 +3689,7 @@ static int run_levels(sre_ctx *ctx, uint64_t n, node_rec *d_recs, uint8_t *d_dep
             return -1;
         // 4. branch pipeline: group starts -> assemble -> hash, chunked so
         // the 552-B scratch slots stay bounded.
-        const uint64_t BR_CHUNK =
-            (uint64_t)(SRE_BR_CHUNK_MB) << 20;
+        const uint64_t BR_CHUNK = br_chunk_groups();
         HIP_CHECK(ctx, newn.alloc((uint64_t)n_groups * sizeof(node_rec)));
         HIP_CHECK(ctx, gs.alloc(((uint64_t)n_groups + 1) * 4));
         uint64_t chunk = n_groups < BR_CHUNK ? n_groups : BR_CHUNK;
@@ -3687,7 +3714,7 @@ static int run_levels(sre_ctx *ctx, uint64_t n, node_rec *d_recs, uint8_t *d_dep
         // heavy, stream2) is then pipelined against the hash (VALU heavy,
         // main stream) with ping-pong scratch/meta buffers.
         DBuf perm(ctx), ccnt(ctx), coff(ctx), scratch2(ctx), meta2(ctx);
-        const uint32_t CLS_MIN = 1u << 14; // below this the win is noise
+        const uint64_t CLS_MIN = cls_min_groups();
         bool use_cls = n_groups >= CLS_MIN;
         // fused 1-block kernel handles the class-0 slice of each chunk on
         // the main stream (classes 1-3 keep the split assemble/hash
@@ -3736,6 +3763,8 @@ static int run_levels(sre_ctx *ctx, uint64_t n, node_rec *d_recs, uint8_t *d_dep
                                                    ? SLOT_BR_ROW : SLOT_BR)));
             HIP_CHECK(ctx, meta2.alloc(chunk * sizeof(br_meta)));
         }
+        ctx->path_cnt[0] += use_cls;
+        ctx->path_cnt[3] += pipe2;
         hipEvent_t ev_asm[2], ev_hash[2];
         for (int b = 0; b < 2; ++b) {
             hipEventCreateWithFlags(&ev_asm[b], hipEventDisableTiming);
@@ -3767,6 +3796,8 @@ static int run_levels(sre_ctx *ctx, uint64_t n, node_rec *d_recs, uint8_t *d_dep
                                                           100)
                                              : c0;
             uint32_t c0t = c0 - c0m;
+            ctx->path_cnt[1] += c0;
+            ctx->path_cnt[2]++;
             uint32_t *d_perm = use_cls ? perm.as<uint32_t>() + g0 + c0
                                        : nullptr;
             hipStream_t s_asm = pipe2 ? ctx->stream2 : ctx->stream;
@@ -4574,6 +4605,7 @@ extern "C" int sre_account_proof(sre_ctx *ctx, const uint8_t *targets,
                                  uint64_t cap_lens, uint32_t *out_counts)
 {
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
     if (n_targets == 0 || n_targets > 4096) {
         set_err(ctx, "sre_account_proof: 1..4096 targets");
         return -1;
@@ -4751,6 +4783,7 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
                                  uint64_t cap_lens, uint32_t *out_counts)
 {
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
     if (ctx->na == 0 || ctx->ns == 0) {
         set_err(ctx, "sre_storage_proof: no storage resident");
         return -1;
@@ -4932,6 +4965,7 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
 extern "C" int sre_root(sre_ctx *ctx, uint8_t out_root[32])
 {
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
     memset(&ctx->stats, 0, sizeof(ctx->stats));
     if (ctx->na == 0) {
         if (ctx->ns != 0) {
@@ -4983,6 +5017,7 @@ extern "C" int sre_root(sre_ctx *ctx, uint8_t out_root[32])
 extern "C" int sre_storage_roots(sre_ctx *ctx, uint8_t *out, uint64_t n)
 {
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
     if (n != ctx->na) {
         set_err(ctx, "sre_storage_roots: n != uploaded account count");
         return -1;
@@ -5007,6 +5042,7 @@ extern "C" int sre_subtree_roots(sre_ctx *ctx, uint8_t out_child_refs[16][33],
                                  uint8_t out_root_hash[16][32], uint64_t out_counts[16])
 {
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
     memset(&ctx->stats, 0, sizeof(ctx->stats));
     memset(out_child_lens, 0, 16);
     memset(out_counts, 0, 16 * 8);
@@ -5629,6 +5665,7 @@ static int apply_delta_small(sre_ctx *ctx, const sre_account_delta *acct_delta,
 extern "C" int sre_root_retaining(sre_ctx *ctx, uint8_t out_root[32])
 {
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
     memset(&ctx->stats, 0, sizeof(ctx->stats));
     ctx->cells_valid = false;
     ctx->snap_valid = false;
@@ -5700,6 +5737,7 @@ static int incremental_root_impl(sre_ctx *ctx,
                                  std::vector<uint8_t> *bitmap_out)
 {
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
     if (!ctx->cells_valid) {
         set_err(ctx, "sre_incremental_root: needs sre_root_retaining first");
         return -1;
@@ -6191,6 +6229,7 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
                                    uint64_t n_st, uint8_t out_root[32])
 {
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
     memset(&ctx->stats, 0, sizeof(ctx->stats));
     ctx->cells_valid = false;
     ctx->snap_valid = false;
@@ -6394,5 +6433,11 @@ extern "C" int sre_updates_get(sre_ctx *ctx, sre_update_row *out, uint64_t max_r
 extern "C" int sre_get_stats(sre_ctx *ctx, sre_stats *out)
 {
     *out = ctx->stats;
+    return 0;
+}
+
+extern "C" int sre_get_path_counters(sre_ctx *ctx, uint64_t out[4])
+{
+    memcpy(out, ctx->path_cnt, sizeof(ctx->path_cnt));
     return 0;
 }

@@ -399,3 +399,12 @@ class StateRootEngine:
         self._check(self._lib.sre_get_stats(ctypes.c_void_p(self._ctx),
                                             ctypes.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in SreStats._fields_}
+
+    def path_counters(self) -> dict:
+        """Which branch-pipeline paths the last root-type call took
+        (include/sre.h sre_get_path_counters)."""
+        out = (ctypes.c_uint64 * 4)()
+        self._check(self._lib.sre_get_path_counters(
+            ctypes.c_void_p(self._ctx), out))
+        return {"class_levels": out[0], "fused_groups": out[1],
+                "chunks": out[2], "pipe2_levels": out[3]}

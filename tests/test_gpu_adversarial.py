@@ -3,6 +3,9 @@ sibling fans — shapes the uniform random generator rarely produces.
 
 All states are built CPU-side with crafted keys, checked bit-exact:
 engine (C-ABI) == C oracle == (transitively) pyref.
+
+The builders return the account list so other suites (the pipeline-gate
+tests) can run the same shapes.
 """
 import numpy as np
 import pytest
@@ -38,7 +41,7 @@ def _check(eng, accounts):
     assert eng.finish_top(refs, lens, roots, counts) == want
 
 
-def test_deep_shared_prefixes(eng):
+def deep_shared_prefixes():
     """Keys agreeing on 40-63 nibbles: branches at extreme depths, long
     extension nodes, 1-nibble short keys."""
     base = bind.keccak256(b"deep")
@@ -47,10 +50,14 @@ def test_deep_shared_prefixes(eng):
         accounts.append(_acct(base[:31] + bytes([last])))       # diverge at nibble 62/63
     for mid in [0x00, 0x80]:
         accounts.append(_acct(base[:20] + bytes([mid]) + base[21:]))  # nibble 40
-    _check(eng, accounts)
+    return accounts
 
 
-def test_full_sibling_fan(eng):
+def test_deep_shared_prefixes(eng):
+    _check(eng, deep_shared_prefixes())
+
+
+def full_sibling_fan():
     """A branch with all 16 children at several depths."""
     base = bind.keccak256(b"fan")
     accounts = []
@@ -60,10 +67,14 @@ def test_full_sibling_fan(eng):
         k = bytearray(base)
         k[15] = (k[15] & 0xF0) | n1
         accounts.append(_acct(bytes(k)))
-    _check(eng, accounts)
+    return accounts
 
 
-def test_ragged_storage(eng):
+def test_full_sibling_fan(eng):
+    _check(eng, full_sibling_fan())
+
+
+def ragged_storage():
     """Accounts with 0 / 1 / 2 / 333 slots, plus deep-prefix slot keys."""
     accounts = []
     for i in range(12):
@@ -79,10 +90,14 @@ def test_ragged_storage(eng):
             slots = {bind.keccak256(bytes([i]) + j.to_bytes(2, "little")): j + 1
                      for j in range(333)}
         accounts.append(_acct(key, slots=slots))
-    _check(eng, accounts)
+    return accounts
 
 
-def test_value_rlp_boundaries(eng):
+def test_ragged_storage(eng):
+    _check(eng, ragged_storage())
+
+
+def value_rlp_boundaries():
     """Storage values at every RLP encoding boundary."""
     key = bind.keccak256(b"vals")
     vals = [1, 0x7F, 0x80, 0xFF, 0x100, 0xFFFF, 0x10000,
@@ -93,10 +108,14 @@ def test_value_rlp_boundaries(eng):
                 _acct(bind.keccak256(b"other"), nonce=0, bal=0x7F),
                 _acct(bind.keccak256(b"rich"), nonce=(1 << 64) - 1,
                       bal=(1 << 256) - 1)]
-    _check(eng, accounts)
+    return accounts
 
 
-def test_inline_node_chains(eng):
+def test_value_rlp_boundaries(eng):
+    _check(eng, value_rlp_boundaries())
+
+
+def inline_node_chains():
     """Tiny values + deep divergence: inline (<32 B) leaf and branch nodes
     embedded in parents rather than hashed."""
     accounts = []
@@ -110,7 +129,11 @@ def test_inline_node_chains(eng):
         k[31] = (7 * i + 3) % 256
         slots[bytes(k)] = i + 1
     accounts.append(_acct(key, slots=slots))
-    _check(eng, accounts)
+    return accounts
+
+
+def test_inline_node_chains(eng):
+    _check(eng, inline_node_chains())
 
 
 def test_medium_64slot_parity(eng):

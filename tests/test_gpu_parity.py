@@ -26,15 +26,43 @@ def eng():
 
 def test_keccak_kernel_parity(eng):
     rng = np.random.default_rng(11)
-    for msg_len in [1, 7, 8, 16, 20, 32, 55, 56, 64, 100, 135]:
-        n = 4096
-        msgs = rng.integers(0, 255, (n, msg_len), dtype=np.uint8)
+
+    def run(n, msg_len, stride):
+        # device buffers are padded to a whole number of 256-thread blocks:
+        # the rows past n belong to no message, and the output rows past n
+        # must come back untouched (the kernel's `i >= n` guard)
+        n_pad = (n + 255) // 256 * 256 + 256
+        msgs = rng.integers(0, 256, (n_pad, stride), dtype=np.uint8)
         t = torch.from_numpy(msgs).cuda()
-        out = torch.empty((n, 32), dtype=torch.uint8, device="cuda")
-        eng.keccak_batch_device(t, msg_len, out)
-        want = bind.keccak256_batch(msgs)
+        out = torch.full((n_pad, 32), 0xA5, dtype=torch.uint8, device="cuda")
+        eng.keccak_batch_device(t[:n], msg_len, out[:n])
+        if msg_len:
+            want = bind.keccak256_batch(
+                np.ascontiguousarray(msgs[:n, :msg_len]))
+        else:
+            want = np.tile(np.frombuffer(bind.keccak256(b""), np.uint8),
+                           (n, 1))
         got = out.cpu().numpy()
-        assert np.array_equal(got, want), f"len={msg_len}"
+        tag = f"len={msg_len} n={n} stride={stride}"
+        assert np.array_equal(got[:n], want), tag
+        assert (got[n:] == 0xA5).all(), "wrote past n: " + tag
+
+    lens = [1, 7, 8, 16, 20, 32, 55, 56, 64, 100, 127, 128, 134, 135]
+    for msg_len in lens:
+        for n in [1, 255, 257, 4096]:
+            run(n, msg_len, msg_len)
+    # row stride > len: bytes between messages must not be absorbed
+    run(257, 100, 109)
+    run(4096, 135, 136)
+    # the empty message (len 0 is accepted; a row still needs a stride)
+    for n in [1, 257]:
+        run(n, 0, 8)
+    assert 255 in rng.integers(0, 256, 4096, dtype=np.uint8)  # full byte range
+    # one keccak block only: 136 and up is rejected, not truncated
+    t = torch.zeros((4, 136), dtype=torch.uint8, device="cuda")
+    out = torch.empty((4, 32), dtype=torch.uint8, device="cuda")
+    with pytest.raises(RuntimeError):
+        eng.keccak_batch_device(t, 136, out)
 
 
 @pytest.mark.parametrize("name", ["mainnet", "sepolia", "holesky"])
