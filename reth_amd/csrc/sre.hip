@@ -3067,6 +3067,14 @@ __global__ void k_scan_add(uint32_t *__restrict__ out, uint64_t n,
         }                                                                        \
     } while (0)
 
+// Launch a kernel (no dynamic LDS) and check the launch, like HIP_CHECK.
+#define LAUNCH(ctx, kernel, grid, block, stream, ...)                            \
+    do {                                                                         \
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream,           \
+                           __VA_ARGS__);                                         \
+        HIP_CHECK(ctx, hipGetLastError());                                       \
+    } while (0)
+
 // One stored row of the CURRENT trie, as (sort key, 64-bit content hash):
 // the retained row-set snapshot that lets the incremental mode emit a NET
 // TrieUpdates diff (upserts/removals) per delta. Content equality by h64
@@ -3270,9 +3278,9 @@ extern "C" void sre_destroy(sre_ctx *ctx)
         (void)hipFree(e.second);
     ctx->pool.clear();
     if (ctx->stream)
-        hipStreamDestroy(ctx->stream);
+        (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2)
-        hipStreamDestroy(ctx->stream2);
+        (void)hipStreamDestroy(ctx->stream2);
     delete ctx;
 }
 
@@ -3288,77 +3296,88 @@ static int check_cap(sre_ctx *ctx, uint64_t n)
     return 0;
 }
 
-extern "C" int sre_upload_accounts(sre_ctx *ctx, const sre_account_entry *entries,
-                                   uint64_t n)
+// The resident state changed (or is about to): nothing retained for the
+// incremental modes matches it any more.
+static void invalidate_retention(sre_ctx *ctx)
 {
-    if (check_cap(ctx, n))
-        return -1;
     ctx->cells_valid = false;
     ctx->snap_valid = false;
     ctx->lcp_valid = false;
+}
+
+// Start of a root-type call: select the device, reset the path counters
+// and (for the calls that publish them) the stats.
+static int begin_call(sre_ctx *ctx, bool zero_stats)
+{
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    release_acct(ctx);
+    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
+    if (zero_stats)
+        memset(&ctx->stats, 0, sizeof(ctx->stats));
+    return 0;
+}
+
+// Replace one resident input array (accounts or storage; `release` frees
+// the previous one) with an engine-owned copy of host entries.
+template <typename T>
+static int upload_entries(sre_ctx *ctx, void (*release)(sre_ctx *), const T **d,
+                          uint64_t *count, bool *own, const T *entries, uint64_t n)
+{
+    if (check_cap(ctx, n))
+        return -1;
+    invalidate_retention(ctx);
+    HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    release(ctx);
     void *p = nullptr;
     if (n) {
-        HIP_CHECK(ctx, hipMalloc(&p, n * sizeof(sre_account_entry)));
-        HIP_CHECK(ctx, hipMemcpy(p, entries, n * sizeof(sre_account_entry),
-                                 hipMemcpyHostToDevice));
+        HIP_CHECK(ctx, hipMalloc(&p, n * sizeof(T)));
+        HIP_CHECK(ctx, hipMemcpy(p, entries, n * sizeof(T), hipMemcpyHostToDevice));
     }
-    ctx->d_acct = (const sre_account_entry *)p;
-    ctx->na = n;
-    ctx->own_acct = true;
+    *d = (const T *)p;
+    *count = n;
+    *own = true;
     return 0;
+}
+
+// Borrow device-resident inputs (zero-copy; caller keeps them alive).
+template <typename T>
+static int borrow_entries(sre_ctx *ctx, void (*release)(sre_ctx *), const T **d,
+                          uint64_t *count, bool *own, const void *d_entries,
+                          uint64_t n)
+{
+    if (check_cap(ctx, n))
+        return -1;
+    invalidate_retention(ctx);
+    release(ctx);
+    *d = (const T *)d_entries;
+    *count = n;
+    *own = false;
+    return 0;
+}
+
+extern "C" int sre_upload_accounts(sre_ctx *ctx, const sre_account_entry *entries,
+                                   uint64_t n)
+{
+    return upload_entries(ctx, release_acct, &ctx->d_acct, &ctx->na,
+                          &ctx->own_acct, entries, n);
 }
 
 extern "C" int sre_upload_storage(sre_ctx *ctx, const sre_storage_entry *entries,
                                   uint64_t n)
 {
-    if (check_cap(ctx, n))
-        return -1;
-    ctx->cells_valid = false;
-    ctx->snap_valid = false;
-    ctx->lcp_valid = false;
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    release_st(ctx);
-    void *p = nullptr;
-    if (n) {
-        HIP_CHECK(ctx, hipMalloc(&p, n * sizeof(sre_storage_entry)));
-        HIP_CHECK(ctx, hipMemcpy(p, entries, n * sizeof(sre_storage_entry),
-                                 hipMemcpyHostToDevice));
-    }
-    ctx->d_st = (const sre_storage_entry *)p;
-    ctx->ns = n;
-    ctx->own_st = true;
-    return 0;
+    return upload_entries(ctx, release_st, &ctx->d_st, &ctx->ns, &ctx->own_st,
+                          entries, n);
 }
 
-// Borrow device-resident inputs (zero-copy; caller keeps them alive).
 extern "C" int sre_set_accounts_device(sre_ctx *ctx, const void *d_entries, uint64_t n)
 {
-    if (check_cap(ctx, n))
-        return -1;
-    ctx->cells_valid = false;
-    ctx->snap_valid = false;
-    ctx->lcp_valid = false;
-    release_acct(ctx);
-    ctx->d_acct = (const sre_account_entry *)d_entries;
-    ctx->na = n;
-    ctx->own_acct = false;
-    return 0;
+    return borrow_entries(ctx, release_acct, &ctx->d_acct, &ctx->na,
+                          &ctx->own_acct, d_entries, n);
 }
 
 extern "C" int sre_set_storage_device(sre_ctx *ctx, const void *d_entries, uint64_t n)
 {
-    if (check_cap(ctx, n))
-        return -1;
-    ctx->cells_valid = false;
-    ctx->snap_valid = false;
-    ctx->lcp_valid = false;
-    release_st(ctx);
-    ctx->d_st = (const sre_storage_entry *)d_entries;
-    ctx->ns = n;
-    ctx->own_st = false;
-    return 0;
+    return borrow_entries(ctx, release_st, &ctx->d_st, &ctx->ns, &ctx->own_st,
+                          d_entries, n);
 }
 
 extern "C" int sre_keccak_batch_device(sre_ctx *ctx, const void *d_in, uint64_t stride,
@@ -3372,10 +3391,8 @@ extern "C" int sre_keccak_batch_device(sre_ctx *ctx, const void *d_in, uint64_t 
     if (n == 0)
         return 0;
     uint64_t blocks = (n + BLOCK - 1) / BLOCK;
-    hipLaunchKernelGGL(k_keccak_batch, dim3((uint32_t)blocks), dim3(BLOCK), 0,
-                       ctx->stream, (const uint8_t *)d_in, stride, len, n,
-                       (uint8_t *)d_out);
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_keccak_batch, (uint32_t)blocks, BLOCK, ctx->stream,
+           (const uint8_t *)d_in, stride, len, n, (uint8_t *)d_out);
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -3412,17 +3429,66 @@ struct DBuf {
     template <typename T> T *as() { return (T *)p; }
 };
 
-static void swap_bufs(DBuf &a, DBuf &b)
-{
-    std::swap(a.p, b.p);
-    std::swap(a.sz, b.sz);
-}
+// Owning HIP event. A failed create leaves a null event, which the first
+// checked record/wait on it reports.
+struct Event {
+    hipEvent_t ev = nullptr;
+    explicit Event(unsigned flags = hipEventDefault)
+    {
+        (void)hipEventCreateWithFlags(&ev, flags);
+    }
+    ~Event()
+    {
+        if (ev)
+            (void)hipEventDestroy(ev);
+    }
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+};
+
+// Start/stop event pair. Adds no synchronisation: ms() is valid only after
+// the caller has synchronised the stream stop() was recorded on.
+struct EvTimer {
+    Event t0, t1;
+    hipError_t start(hipStream_t s) { return hipEventRecord(t0.ev, s); }
+    hipError_t stop(hipStream_t s) { return hipEventRecord(t1.ev, s); }
+    hipError_t ms(float *out) { return hipEventElapsedTime(out, t0.ev, t1.ev); }
+};
 
 static inline uint32_t grid_for(uint64_t n)
 {
     return (uint32_t)((n + BLOCK - 1) / BLOCK);
 }
 
+// The 4-byte device error flag every pass ORs its E_* bits into.
+static int alloc_err_flag(sre_ctx *ctx, DBuf &err)
+{
+    HIP_CHECK(ctx, err.alloc(4));
+    HIP_CHECK(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
+    return 0;
+}
+
+// Grow a retained (non-pool) device buffer to `want` elements; contents
+// are not preserved. The bigger buffer is allocated, and the stream
+// drained, before the old one is freed: queued work may still read it.
+static int grow_retained(sre_ctx *ctx, void **slot, uint64_t *capacity,
+                         uint64_t want, uint64_t elem_bytes = 1)
+{
+    if (*capacity >= want)
+        return 0;
+    void *bigger = nullptr;
+    HIP_CHECK(ctx, hipMalloc(&bigger, want * elem_bytes));
+    if (*slot) {
+        hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess)
+            (void)hipFree(bigger);
+        HIP_CHECK(ctx, e);
+        (void)hipFree(*slot);
+    }
+    *slot = bigger;
+    *capacity = want;
+    return 0;
+}
 
 // exclusive scan of u32 in[n] -> out[n]; total returned synchronously.
 static int scan_u32(sre_ctx *ctx, const uint32_t *d_in, uint32_t *d_out, uint64_t n,
@@ -3437,17 +3503,15 @@ static int scan_u32(sre_ctx *ctx, const uint32_t *d_in, uint32_t *d_out, uint64_
     uint64_t nblocks = (n + per_block - 1) / per_block;
     DBuf sums(ctx), sums_scanned(ctx);
     HIP_CHECK(ctx, sums.alloc(nblocks * 4));
-    hipLaunchKernelGGL(k_scan_block, dim3((uint32_t)nblocks), dim3(BLOCK), 0,
-                       ctx->stream, d_in, n, d_out, sums.as<uint32_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_scan_block, (uint32_t)nblocks, BLOCK, ctx->stream, d_in, n,
+           d_out, sums.as<uint32_t>());
     if (nblocks > 1) {
         HIP_CHECK(ctx, sums_scanned.alloc(nblocks * 4));
         if (scan_u32(ctx, sums.as<uint32_t>(), sums_scanned.as<uint32_t>(), nblocks,
                      total))
             return -1;
-        hipLaunchKernelGGL(k_scan_add, dim3(grid_for(n)), dim3(BLOCK), 0, ctx->stream,
-                           d_out, n, sums_scanned.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_scan_add, grid_for(n), BLOCK, ctx->stream, d_out, n,
+               sums_scanned.as<uint32_t>());
     } else if (total) {
         HIP_CHECK(ctx, hipMemcpyAsync(total, sums.as<uint32_t>(), 4,
                                       hipMemcpyDeviceToHost, ctx->stream));
@@ -3488,26 +3552,489 @@ static uint64_t br_chunk_groups()
     return v < 256 ? 256 : (uint64_t)v;
 }
 
-// updates_kind: -1 = off; 0/1 = retain TrieUpdates rows of this trie kind
-// (d_bhash then holds 32 B per underlying entry for branch-hash lookups).
-static int run_levels(sre_ctx *ctx, uint64_t n, node_rec *d_recs, uint8_t *d_depths,
-                      const int8_t *d_lcp, const uint8_t *d_keys, uint64_t key_stride,
-                      const uint32_t *hist_host, int subtree, uint8_t *d_seg_roots,
-                      uint8_t *d_child_refs, uint8_t *d_child_lens, uint32_t *d_err,
-                      pass_out *po, int updates_kind, uint8_t *d_bhash,
-                      // cell-top capture (dirty-path incremental): when
-                      // capture_depth > 0, every level input at depth
-                      // capture_depth-1 is appended to d_cap (each such
-                      // record's keys share >= capture_depth nibbles: exactly
-                      // one cell, disjoint from every other captured row)
-                      int capture_depth = 0, cap_row *d_cap = nullptr,
-                      uint32_t *d_cap_cnt = nullptr, uint64_t cap_capacity = 0,
-                      // account multiproof capture (sre_account_proof)
-                      const uint32_t *d_pti = nullptr, uint32_t n_pt = 0,
-                      proof_row *d_prows = nullptr,
-                      uint32_t *d_prow_cnt = nullptr, uint32_t prow_cap = 0,
-                      const uint32_t *d_pti2 = nullptr)
+// Required inputs of run_levels: the leaf records of one trie family (every
+// storage trie, or the account trie) and where its roots go.
+struct level_in {
+    uint64_t n = 0;
+    node_rec *recs = nullptr;
+    uint8_t *depths = nullptr;
+    const int8_t *lcp = nullptr;
+    const uint8_t *keys = nullptr; // entry i's key at keys + i * key_stride
+    uint64_t key_stride = 0;
+    const uint32_t *hist_host = nullptr; // records per depth bucket [66]
+    int subtree = 0;
+    uint8_t *seg_roots = nullptr, *child_refs = nullptr, *child_lens = nullptr;
+    uint32_t *err = nullptr;
+    // -1 = off; 0/1 = retain TrieUpdates rows of this trie kind (bhash then
+    // holds 32 B per underlying entry for branch-hash lookups)
+    int updates_kind = -1;
+    uint8_t *bhash = nullptr;
+};
+
+// Cell-top capture (dirty-path incremental): when depth > 0, every level
+// input at depth depth-1 is appended to rows (each such record's keys share
+// >= depth nibbles: exactly one cell, disjoint from every other captured
+// row). Default: off.
+struct cell_capture {
+    int depth = 0;
+    cap_row *rows = nullptr;
+    uint32_t *count = nullptr;
+    uint64_t capacity = 0;
+};
+
+// Multiproof capture (sre_account_proof / sre_storage_proof): the path-node
+// RLPs of the n targets at entry indices pti / pti2. Default (n == 0): off.
+struct proof_capture {
+    const uint32_t *pti = nullptr, *pti2 = nullptr;
+    uint32_t n = 0;
+    proof_row *rows = nullptr;
+    uint32_t *row_count = nullptr;
+    uint32_t row_cap = 0;
+};
+
+// Per-depth carry RUN LISTS: a branch node produced with parent depth p
+// waits, in place inside its level's depth-bucketed output buffer, as
+// part of a sorted run; level p consumes all its runs with ONE k-way
+// positioning merge. This replaces the eager re-merge of an
+// accumulated carry (each arrival used to re-read/rewrite the whole
+// carry); now every node is positioned exactly once. The output
+// buffers stay alive (pool-backed) until the pass ends.
+struct run_ref {
+    const node_rec *p;
+    const uint32_t *keys; // compact .s array (parallel to p)
+    uint64_t n;
+};
+
+// What run_levels carries from one level to the next.
+struct level_carry {
+    std::vector<run_ref> druns[64];
+    uint64_t drun_total[64] = {0};
+    std::vector<std::unique_ptr<DBuf>> live; // buffers the runs point into
+    DBuf pend; // device counters: [p+1] nodes pending at depth p, [65] blocks
+    uint32_t pending_host[66] = {0};
+    explicit level_carry(sre_ctx *c) : pend(c) {}
+};
+
+// Transient buffers every level re-allocates (pool-backed, so a level
+// usually gets its predecessor's buffer back).
+struct level_bufs {
+    DBuf Lbuf, Cbuf, Ckeys, newn, flags, gidx, gs, scratch, meta, urows,
+        urow_cnt, urowidx;
+    explicit level_bufs(sre_ctx *c)
+        : Lbuf(c), Cbuf(c), Ckeys(c), newn(c), flags(c), gidx(c), gs(c),
+          scratch(c), meta(c), urows(c), urow_cnt(c), urowidx(c)
+    {
+    }
+};
+
+// One level's working set, released when the level ends.
+struct level_work {
+    int d = 0;
+    uint64_t n_level = 0;
+    uint32_t n_level32 = 0; // H2D source of gs[n_groups]: outlives the copy
+    const node_rec *L = nullptr; // merged, sorted level input
+    uint32_t n_groups = 0;
+    uint64_t chunk = 0; // branch-pipeline chunk, in groups
+    bool use_cls = false, use_fused = false, pipe2 = false;
+    DBuf perm, ccnt, coff, scratch2, meta2, cinv;
+    std::vector<uint32_t> c0s; // per chunk: class-0 group count (fused)
+    explicit level_work(sre_ctx *c)
+        : perm(c), ccnt(c), coff(c), scratch2(c), meta2(c), cinv(c)
+    {
+    }
+};
+
+// Stable depth-major bucket of n records into out/out_keys (hist, scan,
+// scatter). The depth comes from d_depths[i] for the leaf records, or, when
+// d_depths is null, from the records themselves (a level's new nodes).
+static int depth_bucket(sre_ctx *ctx, const uint8_t *d_depths,
+                        const node_rec *d_recs, uint64_t n, node_rec *out,
+                        uint32_t *out_keys)
 {
+    uint32_t nblk = grid_for(n);
+    DBuf dc(ctx), do_(ctx);
+    HIP_CHECK(ctx, dc.alloc((uint64_t)66 * nblk * 4));
+    HIP_CHECK(ctx, do_.alloc((uint64_t)66 * nblk * 4));
+    if (d_depths)
+        LAUNCH(ctx, k_depth_hist66, nblk, BLOCK, ctx->stream, d_depths, n, nblk,
+               dc.as<uint32_t>());
+    else
+        LAUNCH(ctx, k_depth_hist66_rec, nblk, BLOCK, ctx->stream, d_recs, n,
+               nblk, dc.as<uint32_t>());
+    uint32_t tot = 0;
+    if (scan_u32(ctx, dc.as<uint32_t>(), do_.as<uint32_t>(), (uint64_t)66 * nblk,
+                 &tot))
+        return -1;
+    if (d_depths)
+        LAUNCH(ctx, k_depth_scatter66, nblk, BLOCK, ctx->stream, d_depths,
+               d_recs, n, nblk, do_.as<uint32_t>(), out, out_keys);
+    else
+        LAUNCH(ctx, k_depth_scatter66_rec, nblk, BLOCK, ctx->stream, d_recs, n,
+               nblk, do_.as<uint32_t>(), out, out_keys);
+    return 0;
+}
+
+// 2-way positioning merge of sorted runs A and B into out; a_keys/b_keys are
+// the runs' compact key arrays (null: read the records).
+static int merge_pair(sre_ctx *ctx, const node_rec *A, uint64_t nA,
+                      const uint32_t *a_keys, const node_rec *B, uint64_t nB,
+                      const uint32_t *b_keys, node_rec *out)
+{
+    LAUNCH(ctx, k_merge_a, grid_for(nA), BLOCK, ctx->stream, A, nA, B, nB, out,
+           b_keys);
+    LAUNCH(ctx, k_merge_b, grid_for(nB), BLOCK, ctx->stream, A, nA, B, nB, out,
+           a_keys);
+    return 0;
+}
+
+// Level d's input: the fresh depth-(d+1) leaf slice (nA records) merged with
+// the runs carried to depth d. The carried runs merge lazily, ONCE, k-way
+// (they are small relative to the fresh slice), then 2-way with the fresh
+// slice so the bulk elements do exactly one positioning search.
+static int merge_level_input(sre_ctx *ctx, level_carry &carry, level_bufs &bufs,
+                             int d, const node_rec *Lslice, const uint32_t *Lkeys,
+                             uint64_t nA, const node_rec **L_out)
+{
+    uint64_t nB = carry.drun_total[d];
+    const std::vector<run_ref> &runs = carry.druns[d];
+    if (nB == 0) {
+        *L_out = Lslice;
+        return 0;
+    }
+    if (nA == 0 && runs.size() == 1) {
+        *L_out = runs[0].p;
+        return 0;
+    }
+    kway_desc kd{};
+    int nr = 0;
+    for (const run_ref &rr : runs) {
+        if (nr < KWAY_MAX) {
+            kd.run[nr] = rr.p;
+            kd.keys[nr] = rr.keys;
+            kd.cnt[nr] = rr.n;
+            nr++;
+        } else {
+            // overflow run (deep tries only): pairwise-merge the
+            // two smallest resident runs to make room
+            int a = 0, b = 1;
+            if (kd.cnt[b] < kd.cnt[a])
+                std::swap(a, b);
+            for (int k = 2; k < nr; ++k) {
+                if (kd.cnt[k] < kd.cnt[a]) {
+                    b = a;
+                    a = k;
+                } else if (kd.cnt[k] < kd.cnt[b]) {
+                    b = k;
+                }
+            }
+            uint64_t tot = kd.cnt[a] + kd.cnt[b];
+            auto mb = std::make_unique<DBuf>(ctx);
+            HIP_CHECK(ctx, mb->alloc(tot * sizeof(node_rec)));
+            if (merge_pair(ctx, kd.run[a], kd.cnt[a], kd.keys[a], kd.run[b],
+                           kd.cnt[b], kd.keys[b], mb->as<node_rec>()))
+                return -1;
+            kd.run[a] = mb->as<node_rec>();
+            kd.keys[a] = nullptr;
+            kd.cnt[a] = tot;
+            carry.live.push_back(std::move(mb));
+            kd.run[b] = rr.p;
+            kd.keys[b] = rr.keys;
+            kd.cnt[b] = rr.n;
+        }
+    }
+    const node_rec *merged;
+    const uint32_t *merged_keys;
+    if (nr == 1) {
+        merged = kd.run[0];
+        merged_keys = kd.keys[0];
+    } else {
+        kd.nruns = nr;
+        kd.acc[0] = 0;
+        for (int k = 0; k < nr; ++k)
+            kd.acc[k + 1] = kd.acc[k] + kd.cnt[k];
+        HIP_CHECK(ctx, bufs.Cbuf.alloc(nB * sizeof(node_rec)));
+        HIP_CHECK(ctx, bufs.Ckeys.alloc(nB * 4));
+        LAUNCH(ctx, k_merge_kway, grid_for(nB), BLOCK, ctx->stream, kd, nB,
+               bufs.Cbuf.as<node_rec>(), bufs.Ckeys.as<uint32_t>());
+        merged = bufs.Cbuf.as<node_rec>();
+        merged_keys = bufs.Ckeys.as<uint32_t>();
+    }
+    if (nA == 0) {
+        *L_out = merged;
+        return 0;
+    }
+    HIP_CHECK(ctx, bufs.Lbuf.alloc((nA + nB) * sizeof(node_rec)));
+    if (merge_pair(ctx, Lslice, nA, Lkeys, merged, nB, merged_keys,
+                   bufs.Lbuf.as<node_rec>()))
+        return -1;
+    *L_out = bufs.Lbuf.as<node_rec>();
+    return 0;
+}
+
+// Group the level input into branch nodes (flags + scan + group starts) and
+// size the buffers of the branch pipeline, which runs in chunks of w.chunk
+// groups so the 552-B scratch slots stay bounded.
+static int find_groups(sre_ctx *ctx, const level_in &in, level_bufs &bufs,
+                       level_work &w)
+{
+    HIP_CHECK(ctx, bufs.flags.alloc(w.n_level * 4));
+    HIP_CHECK(ctx, bufs.gidx.alloc(w.n_level * 4));
+    LAUNCH(ctx, k_group_flags, grid_for(w.n_level), BLOCK, ctx->stream, w.L,
+           w.n_level, in.lcp, w.d, bufs.flags.as<uint32_t>());
+    if (scan_u32(ctx, bufs.flags.as<uint32_t>(), bufs.gidx.as<uint32_t>(),
+                 w.n_level, &w.n_groups))
+        return -1;
+    const uint64_t BR_CHUNK = br_chunk_groups();
+    HIP_CHECK(ctx, bufs.newn.alloc((uint64_t)w.n_groups * sizeof(node_rec)));
+    HIP_CHECK(ctx, bufs.gs.alloc(((uint64_t)w.n_groups + 1) * 4));
+    w.chunk = w.n_groups < BR_CHUNK ? w.n_groups : BR_CHUNK;
+    HIP_CHECK(ctx, bufs.scratch.alloc(w.chunk * (SRE_SCRATCH_ROWMAJOR
+                                                     ? SLOT_BR_ROW : SLOT_BR)));
+    HIP_CHECK(ctx, bufs.meta.alloc(w.chunk * sizeof(br_meta)));
+    if (in.updates_kind >= 0) {
+        // per-level: capacity must cover THIS level's chunk
+        HIP_CHECK(ctx, bufs.urows.alloc(w.chunk * sizeof(sre_update_row)));
+        HIP_CHECK(ctx, bufs.urow_cnt.alloc(4));
+        HIP_CHECK(ctx, bufs.urowidx.alloc(w.chunk * 4));
+    }
+    LAUNCH(ctx, k_group_starts, grid_for(w.n_level), BLOCK, ctx->stream,
+           bufs.flags.as<uint32_t>(), bufs.gidx.as<uint32_t>(), w.n_level,
+           bufs.gs.as<uint32_t>());
+    w.n_level32 = (uint32_t)w.n_level;
+    HIP_CHECK(ctx, hipMemcpyAsync(bufs.gs.as<uint32_t>() + w.n_groups,
+                                  &w.n_level32, 4, hipMemcpyHostToDevice,
+                                  ctx->stream));
+    return 0;
+}
+
+// Class partition (see nmem_class): one perm per chunk makes
+// assemble/hash waves block-count uniform. All chunks' perms are
+// built upfront on the main stream; the per-chunk assemble (memory
+// heavy, stream2) is then pipelined against the hash (VALU heavy,
+// main stream) with ping-pong scratch/meta buffers.
+static int partition_classes(sre_ctx *ctx, const level_in &in, uint32_t n_pt,
+                             level_bufs &bufs, level_work &w)
+{
+    const uint64_t CLS_MIN = cls_min_groups();
+    w.use_cls = w.n_groups >= CLS_MIN;
+    // fused 1-block kernel handles the class-0 slice of each chunk on
+    // the main stream (classes 1-3 keep the split assemble/hash
+    // pipeline); meta/scratch are produced inside the fused kernel, so
+    // updates/proof modes (which read them across kernels) disable it
+    w.use_fused = w.use_cls && n_pt == 0 && in.updates_kind < 0 &&
+                  getenv("SRE_NO_FUSED") == nullptr;
+    if (w.use_cls && n_pt)
+        HIP_CHECK(ctx, w.cinv.alloc((uint64_t)w.n_groups * 4));
+    if (w.use_cls) {
+        HIP_CHECK(ctx, w.perm.alloc((uint64_t)w.n_groups * 4));
+        uint32_t nblk_max = (uint32_t)((w.chunk + CLS_BLOCK - 1) / CLS_BLOCK);
+        HIP_CHECK(ctx, w.ccnt.alloc((uint64_t)4 * nblk_max * 4));
+        HIP_CHECK(ctx, w.coff.alloc((uint64_t)4 * nblk_max * 4));
+        for (uint64_t g0 = 0; g0 < w.n_groups; g0 += w.chunk) {
+            uint32_t gc = (uint32_t)(w.n_groups - g0 < w.chunk ? w.n_groups - g0
+                                                               : w.chunk);
+            uint32_t nblk = (gc + CLS_BLOCK - 1) / CLS_BLOCK;
+            LAUNCH(ctx, k_class_hist, nblk, CLS_BLOCK, ctx->stream,
+                   bufs.gs.as<uint32_t>() + g0, gc, nblk, w.ccnt.as<uint32_t>());
+            uint32_t tot = 0;
+            if (scan_u32(ctx, w.ccnt.as<uint32_t>(), w.coff.as<uint32_t>(),
+                         (uint64_t)4 * nblk, &tot))
+                return -1;
+            LAUNCH(ctx, k_class_scatter, nblk, CLS_BLOCK, ctx->stream,
+                   bufs.gs.as<uint32_t>() + g0, gc, nblk, w.coff.as<uint32_t>(),
+                   w.perm.as<uint32_t>() + g0,
+                   n_pt ? w.cinv.as<uint32_t>() + g0 : nullptr);
+            if (w.use_fused) { // class-0 count = start offset of class 1
+                uint32_t c0 = 0;
+                HIP_CHECK(ctx, hipMemcpy(&c0, w.coff.as<uint32_t>() + nblk, 4,
+                                         hipMemcpyDeviceToHost));
+                w.c0s.push_back(c0);
+            }
+        }
+    }
+    w.pipe2 = w.n_groups > w.chunk; // >1 chunk: overlap pays for 2nd buf
+    if (w.pipe2) {
+        HIP_CHECK(ctx, w.scratch2.alloc(w.chunk * (SRE_SCRATCH_ROWMAJOR
+                                                       ? SLOT_BR_ROW : SLOT_BR)));
+        HIP_CHECK(ctx, w.meta2.alloc(w.chunk * sizeof(br_meta)));
+    }
+    ctx->path_cnt[0] += w.use_cls;
+    ctx->path_cnt[3] += w.pipe2;
+    return 0;
+}
+
+// Branch pipeline over the level's groups, chunk by chunk: assemble ->
+// (proof grab, update rows) -> hash, the fused kernel taking the class-0
+// slice. Records timer start/stop around it on the main stream; the caller
+// synchronises.
+static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
+                             const proof_capture &proof, level_carry &carry,
+                             level_bufs &bufs, level_work &w, EvTimer &timer)
+{
+    const int d = w.d;
+    const uint64_t chunk = w.chunk;
+    const bool pipe2 = w.pipe2, updates = in.updates_kind >= 0;
+    uint32_t *gs = bufs.gs.as<uint32_t>();
+    node_rec *newn = bufs.newn.as<node_rec>();
+    uint32_t *pend = carry.pend.as<uint32_t>();
+    Event ev_asm[2] = {Event(hipEventDisableTiming), Event(hipEventDisableTiming)};
+    Event ev_hash[2] = {Event(hipEventDisableTiming),
+                        Event(hipEventDisableTiming)};
+    // stream2 must not outrun state main-stream work this level depends
+    // on (L, gs, perm are ready once the partition above completes)
+    HIP_CHECK(ctx, hipEventRecord(ev_hash[0].ev, ctx->stream));
+    HIP_CHECK(ctx, hipEventRecord(ev_hash[1].ev, ctx->stream));
+    HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, ev_hash[0].ev, 0));
+    int chunk_i = 0;
+    HIP_CHECK(ctx, timer.start(ctx->stream));
+    for (uint64_t g0 = 0; g0 < w.n_groups; g0 += chunk, ++chunk_i) {
+        uint32_t gc = (uint32_t)(w.n_groups - g0 < chunk ? w.n_groups - g0
+                                                         : chunk);
+        int buf = chunk_i & 1;
+        uint8_t *scr = (pipe2 && buf) ? w.scratch2.as<uint8_t>()
+                                      : bufs.scratch.as<uint8_t>();
+        br_meta *mt = (pipe2 && buf) ? w.meta2.as<br_meta>()
+                                     : bufs.meta.as<br_meta>();
+        // class-0 slice -> fused kernel (main stream); classes 1-3 ->
+        // split assemble (stream2) / hash (main), overlapped
+        uint32_t c0 = w.use_fused ? w.c0s[chunk_i] : 0;
+        uint32_t gsplit = gc - c0;
+        // split the fused class-0 work across both streams so it
+        // overlaps the split hash instead of serializing on main:
+        // main runs fused[0,c0m) then (after the assemble event) the
+        // split hash; stream2 runs assemble then fused[c0m,c0)
+        uint32_t c0m = (pipe2 && gsplit) ? (uint32_t)((uint64_t)c0 * 55 / 100)
+                                         : c0;
+        uint32_t c0t = c0 - c0m;
+        ctx->path_cnt[1] += c0;
+        ctx->path_cnt[2]++;
+        uint32_t *d_perm = w.use_cls ? w.perm.as<uint32_t>() + g0 + c0 : nullptr;
+        hipStream_t s_asm = pipe2 ? ctx->stream2 : ctx->stream;
+        if (pipe2) // wait until the hash consuming this buffer finished
+            HIP_CHECK(ctx, hipStreamWaitEvent(s_asm, ev_hash[buf].ev, 0));
+        if (gsplit)
+            LAUNCH(ctx, k_branch_assemble, (gsplit + BLOCK_A - 1) / BLOCK_A,
+                   BLOCK_A, s_asm, w.L, gs + g0, gsplit, in.lcp, in.keys,
+                   in.key_stride, d, scr, chunk, mt, d_perm, in.err);
+        if (pipe2)
+            HIP_CHECK(ctx, hipEventRecord(ev_asm[buf].ev, s_asm));
+        if (c0m)
+            LAUNCH(ctx, k_branch_fused1, grid_for(c0m), BLOCK, ctx->stream, w.L,
+                   gs + g0, c0m, in.lcp, in.keys, in.key_stride, d, in.subtree,
+                   newn + g0, w.perm.as<uint32_t>() + g0, in.seg_roots,
+                   in.child_refs, in.child_lens, pend, in.err);
+        if (c0t)
+            LAUNCH(ctx, k_branch_fused1, grid_for(c0t), BLOCK, s_asm, w.L,
+                   gs + g0, c0t, in.lcp, in.keys, in.key_stride, d, in.subtree,
+                   newn + g0, w.perm.as<uint32_t>() + g0 + c0m, in.seg_roots,
+                   in.child_refs, in.child_lens, pend, in.err);
+        if (pipe2)
+            HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ev_asm[buf].ev, 0));
+        if (proof.n) // multiproof: copy path-node RLPs out of scratch
+            LAUNCH(ctx, k_proof_grab, (proof.n + BLOCK - 1) / BLOCK, BLOCK,
+                   ctx->stream, w.L, gs + g0, gc, mt, scr, chunk,
+                   w.use_cls ? w.cinv.as<uint32_t>() + g0 : nullptr, in.keys,
+                   in.key_stride, proof.pti, proof.pti2, proof.n, proof.rows,
+                   proof.row_count, proof.row_cap, in.err);
+        if (updates) {
+            // emit BEFORE hashing: children's bhash entries must not yet
+            // be overwritten by this level's nodes (shared leftmost s)
+            HIP_CHECK(ctx, hipMemsetAsync(bufs.urow_cnt.p, 0, 4, ctx->stream));
+            LAUNCH(ctx, k_emit_updates, grid_for(gc), BLOCK, ctx->stream, w.L,
+                   gs + g0, gc, mt, in.keys, in.key_stride, in.bhash,
+                   in.updates_kind, bufs.urows.as<sre_update_row>(),
+                   bufs.urow_cnt.as<uint32_t>(), d_perm,
+                   bufs.urowidx.as<uint32_t>());
+        }
+        if (gsplit)
+            LAUNCH(ctx, k_branch_hash, grid_for(gsplit), BLOCK, ctx->stream, scr,
+                   chunk, mt, gsplit, in.keys, in.key_stride, in.subtree,
+                   newn + g0, d_perm, in.seg_roots, in.child_refs,
+                   in.child_lens, pend, in.err, in.bhash,
+                   updates ? bufs.urows.as<sre_update_row>() : nullptr,
+                   updates ? bufs.urowidx.as<uint32_t>() : nullptr);
+        if (pipe2)
+            HIP_CHECK(ctx, hipEventRecord(ev_hash[buf].ev, ctx->stream));
+        if (updates) {
+            uint32_t nrows = 0;
+            HIP_CHECK(ctx, hipMemcpy(&nrows, bufs.urow_cnt.p, 4,
+                                     hipMemcpyDeviceToHost));
+            if (nrows) {
+                size_t old_sz = ctx->updates.size();
+                ctx->updates.resize(old_sz + nrows);
+                HIP_CHECK(ctx, hipMemcpy(ctx->updates.data() + old_sz,
+                                         bufs.urows.p,
+                                         (uint64_t)nrows * sizeof(sre_update_row),
+                                         hipMemcpyDeviceToHost));
+            }
+        }
+    }
+    if (pipe2) { // trailing stream2 fused work must land before the
+                 // level's outputs are consumed
+        HIP_CHECK(ctx, hipEventRecord(ev_asm[0].ev, ctx->stream2));
+        HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ev_asm[0].ev, 0));
+    }
+    HIP_CHECK(ctx, timer.stop(ctx->stream));
+    return 0;
+}
+
+// Distribute level d's new nodes into their target per-depth carries.
+// pend[p+1] - previous snapshot = nodes newly pending at depth p.
+static int distribute_new_nodes(sre_ctx *ctx, level_carry &carry,
+                                level_bufs &bufs, int d, uint32_t n_groups,
+                                uint64_t *branch_blocks)
+{
+    uint32_t *pending_host = carry.pending_host;
+    uint32_t prev_pending[66];
+    memcpy(prev_pending, pending_host, sizeof(prev_pending));
+    HIP_CHECK(ctx, hipMemcpy(pending_host, carry.pend.p, 66 * 4,
+                             hipMemcpyDeviceToHost));
+    pending_host[d + 1] = 0; // consumed (and d's carry was emptied)
+    HIP_CHECK(ctx, hipMemsetAsync((uint8_t *)carry.pend.p + 4 * (d + 1), 0, 4,
+                                  ctx->stream));
+    *branch_blocks = pending_host[65];
+    // one stable depth-major scatter of the outputs; per-depth slices
+    // then wait in place as carried runs — no per-depth rescans.
+    uint64_t fresh_cnt[64] = {0};
+    uint64_t slice_off[66];
+    bool any_fresh = false;
+    uint64_t roots_n = n_groups;
+    for (int p = 0; p < d; ++p) {
+        fresh_cnt[p] = pending_host[p + 1] - prev_pending[p + 1];
+        roots_n -= fresh_cnt[p];
+        any_fresh |= fresh_cnt[p] != 0;
+    }
+    slice_off[0] = 0;
+    slice_off[1] = roots_n; // bucket 0: segment roots, stay put
+    for (int v = 1; v < 65; ++v)
+        slice_off[v + 1] = slice_off[v] + (v - 1 < d ? fresh_cnt[v - 1] : 0);
+    if (!any_fresh)
+        return 0;
+    auto nb = std::make_unique<DBuf>(ctx);
+    auto nbk = std::make_unique<DBuf>(ctx);
+    HIP_CHECK(ctx, nb->alloc((uint64_t)n_groups * sizeof(node_rec)));
+    HIP_CHECK(ctx, nbk->alloc((uint64_t)n_groups * 4));
+    if (depth_bucket(ctx, nullptr, bufs.newn.as<node_rec>(), n_groups,
+                     nb->as<node_rec>(), nbk->as<uint32_t>()))
+        return -1;
+    // record the per-depth slices as carried runs, in place
+    for (int p = 0; p < d; ++p)
+        if (fresh_cnt[p]) {
+            carry.druns[p].push_back({nb->as<node_rec>() + slice_off[p + 1],
+                                      nbk->as<uint32_t>() + slice_off[p + 1],
+                                      fresh_cnt[p]});
+            carry.drun_total[p] += fresh_cnt[p];
+        }
+    carry.live.push_back(std::move(nb));
+    carry.live.push_back(std::move(nbk));
+    return 0;
+}
+
+static int run_levels(sre_ctx *ctx, const level_in &in, pass_out *po,
+                      const cell_capture &cap = {},
+                      const proof_capture &proof = {})
+{
+    const uint32_t *hist_host = in.hist_host;
     int maxd = -1;
     for (int d = 63; d >= 0; --d)
         if (hist_host[d + 1]) {
@@ -3517,471 +4044,65 @@ static int run_levels(sre_ctx *ctx, uint64_t n, node_rec *d_recs, uint8_t *d_dep
     if (maxd < 0)
         return 0; // every leaf was already a segment root
 
-    // Per-depth carry RUN LISTS: a branch node produced with parent depth p
-    // waits, in place inside its level's depth-bucketed output buffer, as
-    // part of a sorted run; level p consumes all its runs with ONE k-way
-    // positioning merge. This replaces the eager re-merge of an
-    // accumulated carry (each arrival used to re-read/rewrite the whole
-    // carry); now every node is positioned exactly once. The output
-    // buffers stay alive (pool-backed) until the pass ends.
-    struct run_ref {
-        const node_rec *p;
-        const uint32_t *keys; // compact .s array (parallel to p)
-        uint64_t n;
-    };
-    std::vector<run_ref> druns[64];
-    uint64_t drun_total[64] = {0};
-    std::vector<std::unique_ptr<DBuf>> live;
-
-    DBuf Lbuf(ctx), Cbuf(ctx), Ckeys(ctx), newn(ctx);
-    DBuf flags(ctx), gidx(ctx), pend(ctx);
-    DBuf gs(ctx), scratch(ctx), meta(ctx), urows(ctx), urow_cnt(ctx),
-        urowidx(ctx);
-    HIP_CHECK(ctx, pend.alloc(66 * 4));
-    HIP_CHECK(ctx, hipMemsetAsync(pend.p, 0, 66 * 4, ctx->stream));
-
-    uint32_t pending_host[66] = {0};
+    level_carry carry(ctx);
+    level_bufs bufs(ctx);
+    HIP_CHECK(ctx, carry.pend.alloc(66 * 4));
+    HIP_CHECK(ctx, hipMemsetAsync(carry.pend.p, 0, 66 * 4, ctx->stream));
     uint64_t branch_blocks_base = po->branch_blocks;
-    hipEvent_t ev0, ev1;
-    hipEventCreate(&ev0);
-    hipEventCreate(&ev1);
+    EvTimer timer;
 
-    // 1. (once) stable depth-major bucket of the leaf records: doff[v] =
+    // (once) stable depth-major bucket of the leaf records: doff[v] =
     // start of the depth-v slice; every level's fresh input is then a slice.
     DBuf dsorted(ctx), dskeys(ctx);
     uint64_t doff[67];
-    {
-        HIP_CHECK(ctx, dsorted.alloc(n * sizeof(node_rec)));
-        HIP_CHECK(ctx, dskeys.alloc(n * 4));
-        uint32_t nblk = (uint32_t)((n + BLOCK - 1) / BLOCK);
-        DBuf dc(ctx), do_(ctx);
-        HIP_CHECK(ctx, dc.alloc((uint64_t)66 * nblk * 4));
-        HIP_CHECK(ctx, do_.alloc((uint64_t)66 * nblk * 4));
-        hipLaunchKernelGGL(k_depth_hist66, dim3(nblk), dim3(BLOCK), 0,
-                           ctx->stream, d_depths, n, nblk, dc.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
-        uint32_t tot = 0;
-        if (scan_u32(ctx, dc.as<uint32_t>(), do_.as<uint32_t>(),
-                     (uint64_t)66 * nblk, &tot))
-            return -1;
-        hipLaunchKernelGGL(k_depth_scatter66, dim3(nblk), dim3(BLOCK), 0,
-                           ctx->stream, d_depths, d_recs, n, nblk,
-                           do_.as<uint32_t>(), dsorted.as<node_rec>(),
-                           dskeys.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
-        doff[0] = 0;
-        for (int v = 0; v < 66; ++v)
-            doff[v + 1] = doff[v] + hist_host[v];
-    }
+    HIP_CHECK(ctx, dsorted.alloc(in.n * sizeof(node_rec)));
+    HIP_CHECK(ctx, dskeys.alloc(in.n * 4));
+    if (depth_bucket(ctx, in.depths, in.recs, in.n, dsorted.as<node_rec>(),
+                     dskeys.as<uint32_t>()))
+        return -1;
+    doff[0] = 0;
+    for (int v = 0; v < 66; ++v)
+        doff[v + 1] = doff[v] + hist_host[v];
 
     for (int d = maxd; d >= 0; --d) {
         uint64_t nA = hist_host[d + 1];
-        uint64_t nB = drun_total[d];
-        if (nA == 0 && nB == 0)
+        if (nA == 0 && carry.drun_total[d] == 0)
             continue;
         po->levels++;
-        uint64_t n_level = nA + nB;
-
-        // 1. this level's fresh leaves: the depth-(d+1) slice of dsorted
-        node_rec *Lslice = dsorted.as<node_rec>() + doff[d + 1];
-        const uint32_t *Lkeys = dskeys.as<uint32_t>() + doff[d + 1];
-        // 2. merge carried runs (lazily, ONCE, k-way — they are small
-        // relative to the fresh slice), then 2-way with the fresh slice so
-        // the bulk elements do exactly one positioning search
-        node_rec *L;
-        if (nB == 0) {
-            L = Lslice;
-        } else if (nA == 0 && druns[d].size() == 1) {
-            L = (node_rec *)druns[d][0].p;
-        } else {
-            kway_desc kd{};
-            int nr = 0;
-            for (const run_ref &rr : druns[d]) {
-                if (nr < KWAY_MAX) {
-                    kd.run[nr] = rr.p;
-                    kd.keys[nr] = rr.keys;
-                    kd.cnt[nr] = rr.n;
-                    nr++;
-                } else {
-                    // overflow run (deep tries only): pairwise-merge the
-                    // two smallest resident runs to make room
-                    int a = 0, b = 1;
-                    if (kd.cnt[b] < kd.cnt[a])
-                        std::swap(a, b);
-                    for (int k = 2; k < nr; ++k) {
-                        if (kd.cnt[k] < kd.cnt[a]) {
-                            b = a;
-                            a = k;
-                        } else if (kd.cnt[k] < kd.cnt[b]) {
-                            b = k;
-                        }
-                    }
-                    uint64_t tot = kd.cnt[a] + kd.cnt[b];
-                    auto mb = std::make_unique<DBuf>(ctx);
-                    HIP_CHECK(ctx, mb->alloc(tot * sizeof(node_rec)));
-                    hipLaunchKernelGGL(k_merge_a, dim3(grid_for(kd.cnt[a])),
-                                       dim3(BLOCK), 0, ctx->stream, kd.run[a],
-                                       kd.cnt[a], kd.run[b], kd.cnt[b],
-                                       mb->as<node_rec>(), kd.keys[b]);
-                    hipLaunchKernelGGL(k_merge_b, dim3(grid_for(kd.cnt[b])),
-                                       dim3(BLOCK), 0, ctx->stream, kd.run[a],
-                                       kd.cnt[a], kd.run[b], kd.cnt[b],
-                                       mb->as<node_rec>(), kd.keys[a]);
-                    HIP_CHECK(ctx, hipGetLastError());
-                    kd.run[a] = mb->as<node_rec>();
-                    kd.keys[a] = nullptr;
-                    kd.cnt[a] = tot;
-                    live.push_back(std::move(mb));
-                    kd.run[b] = rr.p;
-                    kd.keys[b] = rr.keys;
-                    kd.cnt[b] = rr.n;
-                }
-            }
-            const node_rec *carry;
-            const uint32_t *carry_keys;
-            if (nr == 1) {
-                carry = kd.run[0];
-                carry_keys = kd.keys[0];
-            } else {
-                kd.nruns = nr;
-                kd.acc[0] = 0;
-                for (int k = 0; k < nr; ++k)
-                    kd.acc[k + 1] = kd.acc[k] + kd.cnt[k];
-                HIP_CHECK(ctx, Cbuf.alloc(nB * sizeof(node_rec)));
-                HIP_CHECK(ctx, Ckeys.alloc(nB * 4));
-                hipLaunchKernelGGL(k_merge_kway, dim3(grid_for(nB)),
-                                   dim3(BLOCK), 0, ctx->stream, kd, nB,
-                                   Cbuf.as<node_rec>(), Ckeys.as<uint32_t>());
-                HIP_CHECK(ctx, hipGetLastError());
-                carry = Cbuf.as<node_rec>();
-                carry_keys = Ckeys.as<uint32_t>();
-            }
-            if (nA == 0) {
-                L = (node_rec *)carry;
-            } else {
-                HIP_CHECK(ctx, Lbuf.alloc(n_level * sizeof(node_rec)));
-                hipLaunchKernelGGL(k_merge_a, dim3(grid_for(nA)), dim3(BLOCK),
-                                   0, ctx->stream, Lslice, nA, carry, nB,
-                                   Lbuf.as<node_rec>(), carry_keys);
-                hipLaunchKernelGGL(k_merge_b, dim3(grid_for(nB)), dim3(BLOCK),
-                                   0, ctx->stream, Lslice, nA, carry, nB,
-                                   Lbuf.as<node_rec>(), Lkeys);
-                HIP_CHECK(ctx, hipGetLastError());
-                L = Lbuf.as<node_rec>();
-            }
-        }
-        if (capture_depth > 0 && d == capture_depth - 1) {
-            hipLaunchKernelGGL(k_capture_L, dim3(grid_for(n_level)), dim3(BLOCK),
-                               0, ctx->stream, L, n_level, d_keys, key_stride,
-                               d_cap, d_cap_cnt, cap_capacity, d_err,
-                               updates_kind >= 0 ? d_bhash : nullptr);
-            HIP_CHECK(ctx, hipGetLastError());
-        }
-        // 3. group flags + scan
-        HIP_CHECK(ctx, flags.alloc(n_level * 4));
-        HIP_CHECK(ctx, gidx.alloc(n_level * 4));
-        hipLaunchKernelGGL(k_group_flags, dim3(grid_for(n_level)), dim3(BLOCK), 0,
-                           ctx->stream, L, n_level, d_lcp, d, flags.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
-        uint32_t n_groups = 0;
-        if (scan_u32(ctx, flags.as<uint32_t>(), gidx.as<uint32_t>(), n_level,
-                     &n_groups))
+        level_work w(ctx);
+        w.d = d;
+        w.n_level = nA + carry.drun_total[d];
+        // fresh leaves (the depth-(d+1) slice of dsorted) + carried runs
+        if (merge_level_input(ctx, carry, bufs, d,
+                              dsorted.as<node_rec>() + doff[d + 1],
+                              dskeys.as<uint32_t>() + doff[d + 1], nA, &w.L))
             return -1;
-        // 4. branch pipeline: group starts -> assemble -> hash, chunked so
-        // the 552-B scratch slots stay bounded.
-        const uint64_t BR_CHUNK = br_chunk_groups();
-        HIP_CHECK(ctx, newn.alloc((uint64_t)n_groups * sizeof(node_rec)));
-        HIP_CHECK(ctx, gs.alloc(((uint64_t)n_groups + 1) * 4));
-        uint64_t chunk = n_groups < BR_CHUNK ? n_groups : BR_CHUNK;
-        HIP_CHECK(ctx, scratch.alloc(chunk * (SRE_SCRATCH_ROWMAJOR
-                                              ? SLOT_BR_ROW : SLOT_BR)));
-        HIP_CHECK(ctx, meta.alloc(chunk * sizeof(br_meta)));
-        if (updates_kind >= 0) {
-            // per-level: capacity must cover THIS level's chunk
-            HIP_CHECK(ctx, urows.alloc(chunk * sizeof(sre_update_row)));
-            HIP_CHECK(ctx, urow_cnt.alloc(4));
-            HIP_CHECK(ctx, urowidx.alloc(chunk * 4));
-        }
-        hipLaunchKernelGGL(k_group_starts, dim3(grid_for(n_level)), dim3(BLOCK), 0,
-                           ctx->stream, flags.as<uint32_t>(), gidx.as<uint32_t>(),
-                           n_level, gs.as<uint32_t>());
-        uint32_t n_level32 = (uint32_t)n_level;
-        HIP_CHECK(ctx, hipMemcpyAsync(gs.as<uint32_t>() + n_groups, &n_level32, 4,
-                                      hipMemcpyHostToDevice, ctx->stream));
-        // class partition (see nmem_class): one perm per chunk makes
-        // assemble/hash waves block-count uniform. All chunks' perms are
-        // built upfront on the main stream; the per-chunk assemble (memory
-        // heavy, stream2) is then pipelined against the hash (VALU heavy,
-        // main stream) with ping-pong scratch/meta buffers.
-        DBuf perm(ctx), ccnt(ctx), coff(ctx), scratch2(ctx), meta2(ctx);
-        const uint64_t CLS_MIN = cls_min_groups();
-        bool use_cls = n_groups >= CLS_MIN;
-        // fused 1-block kernel handles the class-0 slice of each chunk on
-        // the main stream (classes 1-3 keep the split assemble/hash
-        // pipeline); meta/scratch are produced inside the fused kernel, so
-        // updates/proof modes (which read them across kernels) disable it
-        bool use_fused = use_cls && n_pt == 0 && updates_kind < 0 &&
-                         getenv("SRE_NO_FUSED") == nullptr;
-        std::vector<uint32_t> c0s;
-        DBuf cinv(ctx);
-        if (use_cls && n_pt)
-            HIP_CHECK(ctx, cinv.alloc((uint64_t)n_groups * 4));
-        if (use_cls) {
-            HIP_CHECK(ctx, perm.alloc((uint64_t)n_groups * 4));
-            uint32_t nblk_max = (uint32_t)((chunk + CLS_BLOCK - 1) / CLS_BLOCK);
-            HIP_CHECK(ctx, ccnt.alloc((uint64_t)4 * nblk_max * 4));
-            HIP_CHECK(ctx, coff.alloc((uint64_t)4 * nblk_max * 4));
-            for (uint64_t g0 = 0; g0 < n_groups; g0 += chunk) {
-                uint32_t gc = (uint32_t)(n_groups - g0 < chunk ? n_groups - g0
-                                                               : chunk);
-                uint32_t nblk = (gc + CLS_BLOCK - 1) / CLS_BLOCK;
-                hipLaunchKernelGGL(k_class_hist, dim3(nblk), dim3(CLS_BLOCK), 0,
-                                   ctx->stream, gs.as<uint32_t>() + g0, gc, nblk,
-                                   ccnt.as<uint32_t>());
-                HIP_CHECK(ctx, hipGetLastError());
-                uint32_t tot = 0;
-                if (scan_u32(ctx, ccnt.as<uint32_t>(), coff.as<uint32_t>(),
-                             (uint64_t)4 * nblk, &tot))
-                    return -1;
-                hipLaunchKernelGGL(k_class_scatter, dim3(nblk), dim3(CLS_BLOCK),
-                                   0, ctx->stream, gs.as<uint32_t>() + g0, gc,
-                                   nblk, coff.as<uint32_t>(),
-                                   perm.as<uint32_t>() + g0,
-                                   n_pt ? cinv.as<uint32_t>() + g0 : nullptr);
-                HIP_CHECK(ctx, hipGetLastError());
-                if (use_fused) { // class-0 count = start offset of class 1
-                    uint32_t c0 = 0;
-                    HIP_CHECK(ctx, hipMemcpy(&c0, coff.as<uint32_t>() + nblk,
-                                             4, hipMemcpyDeviceToHost));
-                    c0s.push_back(c0);
-                }
-            }
-        }
-        bool pipe2 = n_groups > chunk; // >1 chunk: overlap pays for 2nd buf
-        if (pipe2) {
-            HIP_CHECK(ctx, scratch2.alloc(chunk * (SRE_SCRATCH_ROWMAJOR
-                                                   ? SLOT_BR_ROW : SLOT_BR)));
-            HIP_CHECK(ctx, meta2.alloc(chunk * sizeof(br_meta)));
-        }
-        ctx->path_cnt[0] += use_cls;
-        ctx->path_cnt[3] += pipe2;
-        hipEvent_t ev_asm[2], ev_hash[2];
-        for (int b = 0; b < 2; ++b) {
-            hipEventCreateWithFlags(&ev_asm[b], hipEventDisableTiming);
-            hipEventCreateWithFlags(&ev_hash[b], hipEventDisableTiming);
-        }
-        // stream2 must not outrun state main-stream work this level depends
-        // on (L, gs, perm are ready once the partition above completes)
-        hipEventRecord(ev_hash[0], ctx->stream);
-        hipEventRecord(ev_hash[1], ctx->stream);
-        hipStreamWaitEvent(ctx->stream2, ev_hash[0], 0);
-        int chunk_i = 0;
-        hipEventRecord(ev0, ctx->stream);
-        for (uint64_t g0 = 0; g0 < n_groups; g0 += chunk, ++chunk_i) {
-            uint32_t gc = (uint32_t)(n_groups - g0 < chunk ? n_groups - g0 : chunk);
-            int buf = chunk_i & 1;
-            uint8_t *scr = (pipe2 && buf) ? scratch2.as<uint8_t>()
-                                          : scratch.as<uint8_t>();
-            br_meta *mt = (pipe2 && buf) ? meta2.as<br_meta>()
-                                         : meta.as<br_meta>();
-            // class-0 slice -> fused kernel (main stream); classes 1-3 ->
-            // split assemble (stream2) / hash (main), overlapped
-            uint32_t c0 = use_fused ? c0s[chunk_i] : 0;
-            uint32_t gsplit = gc - c0;
-            // split the fused class-0 work across both streams so it
-            // overlaps the split hash instead of serializing on main:
-            // main runs fused[0,c0m) then (after the assemble event) the
-            // split hash; stream2 runs assemble then fused[c0m,c0)
-            uint32_t c0m = (pipe2 && gsplit) ? (uint32_t)((uint64_t)c0 * 55 /
-                                                          100)
-                                             : c0;
-            uint32_t c0t = c0 - c0m;
-            ctx->path_cnt[1] += c0;
-            ctx->path_cnt[2]++;
-            uint32_t *d_perm = use_cls ? perm.as<uint32_t>() + g0 + c0
-                                       : nullptr;
-            hipStream_t s_asm = pipe2 ? ctx->stream2 : ctx->stream;
-            if (pipe2) // wait until the hash consuming this buffer finished
-                hipStreamWaitEvent(s_asm, ev_hash[buf], 0);
-            if (gsplit)
-                hipLaunchKernelGGL(k_branch_assemble,
-                                   dim3((gsplit + BLOCK_A - 1) / BLOCK_A),
-                                   dim3(BLOCK_A),
-                                   0, s_asm, L, gs.as<uint32_t>() + g0, gsplit,
-                                   d_lcp, d_keys, key_stride, d, scr,
-                                   chunk, mt, d_perm, d_err);
-            HIP_CHECK(ctx, hipGetLastError());
-            if (pipe2) {
-                hipEventRecord(ev_asm[buf], s_asm);
-            }
-            if (c0m) {
-                hipLaunchKernelGGL(k_branch_fused1, dim3(grid_for(c0m)),
-                                   dim3(BLOCK), 0, ctx->stream, L,
-                                   gs.as<uint32_t>() + g0, c0m, d_lcp, d_keys,
-                                   key_stride, d, subtree,
-                                   newn.as<node_rec>() + g0,
-                                   perm.as<uint32_t>() + g0, d_seg_roots,
-                                   d_child_refs, d_child_lens,
-                                   pend.as<uint32_t>(), d_err);
-                HIP_CHECK(ctx, hipGetLastError());
-            }
-            if (c0t) {
-                hipLaunchKernelGGL(k_branch_fused1, dim3(grid_for(c0t)),
-                                   dim3(BLOCK), 0, s_asm, L,
-                                   gs.as<uint32_t>() + g0, c0t, d_lcp, d_keys,
-                                   key_stride, d, subtree,
-                                   newn.as<node_rec>() + g0,
-                                   perm.as<uint32_t>() + g0 + c0m, d_seg_roots,
-                                   d_child_refs, d_child_lens,
-                                   pend.as<uint32_t>(), d_err);
-                HIP_CHECK(ctx, hipGetLastError());
-            }
-            if (pipe2) {
-                hipStreamWaitEvent(ctx->stream, ev_asm[buf], 0);
-            }
-            if (n_pt) { // multiproof: copy path-node RLPs out of scratch
-                hipLaunchKernelGGL(k_proof_grab,
-                                   dim3((n_pt + BLOCK - 1) / BLOCK), dim3(BLOCK),
-                                   0, ctx->stream, L, gs.as<uint32_t>() + g0, gc,
-                                   mt, scr, chunk,
-                                   use_cls ? cinv.as<uint32_t>() + g0 : nullptr,
-                                   d_keys, key_stride,
-                                   d_pti, d_pti2, n_pt, d_prows, d_prow_cnt,
-                                   prow_cap, d_err);
-                HIP_CHECK(ctx, hipGetLastError());
-            }
-            if (updates_kind >= 0) {
-                // emit BEFORE hashing: children's bhash entries must not yet
-                // be overwritten by this level's nodes (shared leftmost s)
-                HIP_CHECK(ctx, hipMemsetAsync(urow_cnt.p, 0, 4, ctx->stream));
-                hipLaunchKernelGGL(k_emit_updates, dim3(grid_for(gc)), dim3(BLOCK),
-                                   0, ctx->stream, L, gs.as<uint32_t>() + g0, gc,
-                                   mt, d_keys, key_stride, d_bhash,
-                                   updates_kind, urows.as<sre_update_row>(),
-                                   urow_cnt.as<uint32_t>(), d_perm,
-                                   urowidx.as<uint32_t>());
-                HIP_CHECK(ctx, hipGetLastError());
-            }
-            if (gsplit) {
-                hipLaunchKernelGGL(k_branch_hash, dim3(grid_for(gsplit)),
-                                   dim3(BLOCK), 0,
-                                   ctx->stream, scr, chunk, mt,
-                                   gsplit, d_keys, key_stride, subtree,
-                                   newn.as<node_rec>() + g0, d_perm,
-                                   d_seg_roots, d_child_refs,
-                                   d_child_lens, pend.as<uint32_t>(), d_err,
-                                   d_bhash,
-                                   updates_kind >= 0
-                                       ? urows.as<sre_update_row>()
-                                       : nullptr,
-                                   updates_kind >= 0 ? urowidx.as<uint32_t>()
-                                                     : nullptr);
-                HIP_CHECK(ctx, hipGetLastError());
-            }
-            if (pipe2)
-                hipEventRecord(ev_hash[buf], ctx->stream);
-            if (updates_kind >= 0) {
-                uint32_t nrows = 0;
-                HIP_CHECK(ctx, hipMemcpy(&nrows, urow_cnt.p, 4,
-                                         hipMemcpyDeviceToHost));
-                if (nrows) {
-                    size_t old_sz = ctx->updates.size();
-                    ctx->updates.resize(old_sz + nrows);
-                    HIP_CHECK(ctx, hipMemcpy(ctx->updates.data() + old_sz,
-                                             urows.p,
-                                             (uint64_t)nrows * sizeof(sre_update_row),
-                                             hipMemcpyDeviceToHost));
-                }
-            }
-        }
-        if (pipe2) { // trailing stream2 fused work must land before the
-                     // level's outputs are consumed
-            hipEventRecord(ev_asm[0], ctx->stream2);
-            hipStreamWaitEvent(ctx->stream, ev_asm[0], 0);
-        }
-        for (int b = 0; b < 2; ++b) {
-            hipEventDestroy(ev_asm[b]);
-            hipEventDestroy(ev_hash[b]);
-        }
-        hipEventRecord(ev1, ctx->stream);
+        if (cap.depth > 0 && d == cap.depth - 1)
+            LAUNCH(ctx, k_capture_L, grid_for(w.n_level), BLOCK, ctx->stream,
+                   w.L, w.n_level, in.keys, in.key_stride, cap.rows, cap.count,
+                   cap.capacity, in.err,
+                   in.updates_kind >= 0 ? in.bhash : nullptr);
+        if (find_groups(ctx, in, bufs, w) ||
+            partition_classes(ctx, in, proof.n, bufs, w) ||
+            run_branch_chunks(ctx, in, proof, carry, bufs, w, timer))
+            return -1;
         HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         float ms = 0;
-        hipEventElapsedTime(&ms, ev0, ev1);
+        HIP_CHECK(ctx, timer.ms(&ms));
         po->branch_ms += ms;
-        po->branch_count += n_groups;
+        po->branch_count += w.n_groups;
 
         // this level's inputs are consumed (slices stay in their live
         // buffers; freed when the pass ends)
-        druns[d].clear();
-        drun_total[d] = 0;
-
-        // 5. distribute the new nodes into their target per-depth carries.
-        // pend[p+1] - previous snapshot = nodes newly pending at depth p.
-        uint32_t prev_pending[66];
-        memcpy(prev_pending, pending_host, sizeof(prev_pending));
-        HIP_CHECK(ctx, hipMemcpy(pending_host, pend.p, 66 * 4, hipMemcpyDeviceToHost));
-        pending_host[d + 1] = 0; // consumed (and d's carry was emptied above)
-        HIP_CHECK(ctx, hipMemsetAsync((uint8_t *)pend.p + 4 * (d + 1), 0, 4,
-                                      ctx->stream));
-        po->branch_blocks = branch_blocks_base + pending_host[65];
-        // one stable depth-major scatter of the outputs; per-depth slices
-        // then merge (or copy) into their carries — no per-depth rescans.
-        uint64_t fresh_cnt[64] = {0};
-        uint64_t slice_off[66];
-        bool any_fresh = false;
-        {
-            uint64_t roots_n = n_groups;
-            for (int p = 0; p < d; ++p) {
-                fresh_cnt[p] = pending_host[p + 1] - prev_pending[p + 1];
-                roots_n -= fresh_cnt[p];
-                any_fresh |= fresh_cnt[p] != 0;
-            }
-            slice_off[0] = 0;
-            slice_off[1] = roots_n; // bucket 0: segment roots, stay put
-            for (int v = 1; v < 65; ++v)
-                slice_off[v + 1] = slice_off[v] + (v - 1 < d ? fresh_cnt[v - 1]
-                                                             : 0);
-        }
-        if (any_fresh) {
-            auto nb = std::make_unique<DBuf>(ctx);
-            auto nbk = std::make_unique<DBuf>(ctx);
-            HIP_CHECK(ctx, nb->alloc((uint64_t)n_groups * sizeof(node_rec)));
-            HIP_CHECK(ctx, nbk->alloc((uint64_t)n_groups * 4));
-            uint32_t nblk = (uint32_t)((n_groups + BLOCK - 1) / BLOCK);
-            DBuf dc2(ctx), do2(ctx);
-            HIP_CHECK(ctx, dc2.alloc((uint64_t)66 * nblk * 4));
-            HIP_CHECK(ctx, do2.alloc((uint64_t)66 * nblk * 4));
-            hipLaunchKernelGGL(k_depth_hist66_rec, dim3(nblk), dim3(BLOCK), 0,
-                               ctx->stream, newn.as<node_rec>(), n_groups,
-                               nblk, dc2.as<uint32_t>());
-            HIP_CHECK(ctx, hipGetLastError());
-            uint32_t tot = 0;
-            if (scan_u32(ctx, dc2.as<uint32_t>(), do2.as<uint32_t>(),
-                         (uint64_t)66 * nblk, &tot))
-                return -1;
-            hipLaunchKernelGGL(k_depth_scatter66_rec, dim3(nblk), dim3(BLOCK),
-                               0, ctx->stream, newn.as<node_rec>(), n_groups,
-                               nblk, do2.as<uint32_t>(), nb->as<node_rec>(),
-                               nbk->as<uint32_t>());
-            HIP_CHECK(ctx, hipGetLastError());
-            // record the per-depth slices as carried runs, in place
-            node_rec *basep = nb->as<node_rec>();
-            uint32_t *keyp = nbk->as<uint32_t>();
-            for (int p = 0; p < d; ++p)
-                if (fresh_cnt[p]) {
-                    druns[p].push_back({basep + slice_off[p + 1],
-                                        keyp + slice_off[p + 1],
-                                        fresh_cnt[p]});
-                    drun_total[p] += fresh_cnt[p];
-                }
-            live.push_back(std::move(nb));
-            live.push_back(std::move(nbk));
-        }
+        carry.druns[d].clear();
+        carry.drun_total[d] = 0;
+        uint64_t blocks = 0;
+        if (distribute_new_nodes(ctx, carry, bufs, d, w.n_groups, &blocks))
+            return -1;
+        po->branch_blocks = branch_blocks_base + blocks;
     }
-    hipEventDestroy(ev0);
-    hipEventDestroy(ev1);
     for (int p = 0; p < 64; ++p)
-        if (drun_total[p] != 0) {
+        if (carry.drun_total[p] != 0) {
             set_err(ctx, "internal: carry not empty after level 0");
             return -1;
         }
@@ -3992,84 +4113,108 @@ static int run_levels(sre_ctx *ctx, uint64_t n, node_rec *d_recs, uint8_t *d_dep
 // passes
 // ---------------------------------------------------------------------------
 
-static int run_storage_pass(sre_ctx *ctx, uint8_t *d_acct_roots, pass_out *po,
-                            uint32_t *d_err,
-                            const uint32_t *d_pti = nullptr, uint32_t n_pt = 0,
-                            proof_row *d_prows = nullptr,
-                            uint32_t *d_prow_cnt = nullptr,
-                            uint32_t prow_cap = 0,
-                            const uint32_t *d_pti2 = nullptr,
-                            // subset mode (incremental): run over an
-                            // explicit entry array and scatter roots into
-                            // d_acct_roots WITHOUT resetting it first
-                            const sre_storage_entry *d_st_in = nullptr,
-                            uint64_t ns_in = ~0ull)
+static void publish_stats(sre_ctx *ctx, const pass_out &po, double total_ms)
 {
-    uint64_t ns = d_st_in ? ns_in : ctx->ns, na = ctx->na;
-    const sre_storage_entry *d_st = d_st_in ? d_st_in : ctx->d_st;
-    if (!d_st_in) {
-        hipLaunchKernelGGL(k_fill_empty_roots, dim3(grid_for(na)), dim3(BLOCK),
-                           0, ctx->stream, d_acct_roots, na);
-        HIP_CHECK(ctx, hipGetLastError());
+    ctx->stats.total_ms = total_ms;
+    ctx->stats.leaf_hash_ms = po.leaf_ms;
+    ctx->stats.leaf_count = po.leaf_count;
+    ctx->stats.leaf_blocks = po.leaf_blocks;
+    ctx->stats.branch_hash_ms = po.branch_ms;
+    ctx->stats.branch_count = po.branch_count;
+    ctx->stats.branch_blocks = po.branch_blocks;
+    ctx->stats.levels = po.levels;
+}
+
+// A sorted storage array cut into per-account segments (one storage trie
+// each): seg_id[i] = segment of entry i, lcp = neighbour common prefixes
+// (segment-aware), seg_start / seg_acct = first entry / account index per
+// segment.
+struct storage_segs {
+    DBuf flags, seg_id, lcp, seg_start, seg_acct;
+    uint32_t n_seg = 0;
+    explicit storage_segs(sre_ctx *c)
+        : flags(c), seg_id(c), lcp(c), seg_start(c), seg_acct(c)
+    {
     }
+};
+
+// Input-contract violations (unsorted/orphan entries) are flagged in d_err;
+// nothing is synchronised here.
+static int segment_storage(sre_ctx *ctx, const sre_storage_entry *d_st,
+                           uint64_t ns, uint32_t *d_err, storage_segs &sg)
+{
+    HIP_CHECK(ctx, sg.flags.alloc(ns * 4));
+    HIP_CHECK(ctx, sg.seg_id.alloc(ns * 4));
+    HIP_CHECK(ctx, sg.lcp.alloc(ns + 1));
+    LAUNCH(ctx, k_seg_flags_lcp, grid_for(ns + 1), BLOCK, ctx->stream, d_st, ns,
+           sg.flags.as<uint32_t>(), sg.lcp.as<int8_t>(), d_err);
+    // seg_id[i] = inclusive_scan(flags)[i] - 1 (segment index of entry i)
+    if (scan_u32(ctx, sg.flags.as<uint32_t>(), sg.seg_id.as<uint32_t>(), ns,
+                 &sg.n_seg))
+        return -1;
+    LAUNCH(ctx, k_seg_fix, grid_for(ns), BLOCK, ctx->stream,
+           sg.flags.as<uint32_t>(), sg.seg_id.as<uint32_t>(), ns);
+    HIP_CHECK(ctx, sg.seg_start.alloc((uint64_t)sg.n_seg * 4));
+    HIP_CHECK(ctx, sg.seg_acct.alloc((uint64_t)sg.n_seg * 4));
+    LAUNCH(ctx, k_seg_starts, grid_for(ns), BLOCK, ctx->stream,
+           sg.flags.as<uint32_t>(), sg.seg_id.as<uint32_t>(), ns,
+           sg.seg_start.as<uint32_t>());
+    LAUNCH(ctx, k_seg_acct, grid_for(sg.n_seg), BLOCK, ctx->stream, d_st,
+           sg.seg_start.as<uint32_t>(), sg.n_seg, ctx->d_acct, ctx->na,
+           sg.seg_acct.as<uint32_t>(), d_err);
+    return 0;
+}
+
+// Explicit storage entries for run_storage_pass's subset mode (incremental):
+// the pass runs over them instead of the resident array and scatters roots
+// into d_acct_roots WITHOUT resetting it first.
+struct storage_subset {
+    const sre_storage_entry *entries = nullptr;
+    uint64_t n = 0;
+};
+
+static int run_storage_pass(sre_ctx *ctx, uint8_t *d_acct_roots, pass_out *po,
+                            uint32_t *d_err, const proof_capture &proof = {},
+                            const storage_subset &sub = {})
+{
+    const bool subset = sub.entries != nullptr;
+    uint64_t ns = subset ? sub.n : ctx->ns, na = ctx->na;
+    const sre_storage_entry *d_st = subset ? sub.entries : ctx->d_st;
+    if (!subset)
+        LAUNCH(ctx, k_fill_empty_roots, grid_for(na), BLOCK, ctx->stream,
+               d_acct_roots, na);
     if (ns == 0)
         return 0;
 
-    DBuf flags(ctx), seg_id(ctx), lcp(ctx), recs(ctx), depths(ctx), hist(ctx);
-    HIP_CHECK(ctx, flags.alloc(ns * 4));
-    HIP_CHECK(ctx, seg_id.alloc(ns * 4));
-    HIP_CHECK(ctx, lcp.alloc(ns + 1));
+    DBuf recs(ctx), depths(ctx), hist(ctx), seg_roots(ctx);
     HIP_CHECK(ctx, recs.alloc(ns * sizeof(node_rec)));
     HIP_CHECK(ctx, depths.alloc(ns));
     HIP_CHECK(ctx, hist.alloc(66 * 4));
     HIP_CHECK(ctx, hipMemsetAsync(hist.p, 0, 66 * 4, ctx->stream));
-
-    hipLaunchKernelGGL(k_seg_flags_lcp, dim3(grid_for(ns + 1)), dim3(BLOCK), 0,
-                       ctx->stream, d_st, ns, flags.as<uint32_t>(),
-                       lcp.as<int8_t>(), d_err);
-    HIP_CHECK(ctx, hipGetLastError());
-    // seg_id[i] = inclusive_scan(flags)[i] - 1 (segment index of entry i)
-    uint32_t n_seg = 0;
-    if (scan_u32(ctx, flags.as<uint32_t>(), seg_id.as<uint32_t>(), ns, &n_seg))
+    storage_segs sg(ctx);
+    if (segment_storage(ctx, d_st, ns, d_err, sg))
         return -1;
-    hipLaunchKernelGGL(k_seg_fix, dim3(grid_for(ns)), dim3(BLOCK), 0, ctx->stream,
-                       flags.as<uint32_t>(), seg_id.as<uint32_t>(), ns);
-    HIP_CHECK(ctx, hipGetLastError());
-
-    DBuf seg_start(ctx), seg_acct(ctx), seg_roots(ctx);
-    HIP_CHECK(ctx, seg_start.alloc((uint64_t)n_seg * 4));
-    HIP_CHECK(ctx, seg_acct.alloc((uint64_t)n_seg * 4));
+    const uint32_t n_seg = sg.n_seg;
     HIP_CHECK(ctx, seg_roots.alloc((uint64_t)n_seg * 32));
-    hipLaunchKernelGGL(k_seg_starts, dim3(grid_for(ns)), dim3(BLOCK), 0, ctx->stream,
-                       flags.as<uint32_t>(), seg_id.as<uint32_t>(), ns,
-                       seg_start.as<uint32_t>());
-    hipLaunchKernelGGL(k_seg_acct, dim3(grid_for(n_seg)), dim3(BLOCK), 0, ctx->stream,
-                       d_st, seg_start.as<uint32_t>(), n_seg, ctx->d_acct, na,
-                       seg_acct.as<uint32_t>(), d_err);
     // input-contract violations (unsorted/orphan entries) are flagged by the
     // kernels above; bail BEFORE the trie machinery runs on garbage lcps.
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (check_err(ctx, d_err))
         return -1;
 
-    hipEvent_t ev0, ev1;
-    hipEventCreate(&ev0);
-    hipEventCreate(&ev1);
-    hipEventRecord(ev0, ctx->stream);
-    hipLaunchKernelGGL(k_leaf_storage, dim3(grid_for(ns)), dim3(BLOCK), 0, ctx->stream,
-                       d_st, ns, lcp.as<int8_t>(), seg_id.as<uint32_t>(),
-                       recs.as<node_rec>(), depths.as<uint8_t>(), hist.as<uint32_t>(),
-                       seg_roots.as<uint8_t>(), d_err);
-    HIP_CHECK(ctx, hipGetLastError());
-    hipEventRecord(ev1, ctx->stream);
+    EvTimer leaf;
+    HIP_CHECK(ctx, leaf.start(ctx->stream));
+    LAUNCH(ctx, k_leaf_storage, grid_for(ns), BLOCK, ctx->stream, d_st, ns,
+           sg.lcp.as<int8_t>(), sg.seg_id.as<uint32_t>(), recs.as<node_rec>(),
+           depths.as<uint8_t>(), hist.as<uint32_t>(), seg_roots.as<uint8_t>(),
+           d_err);
+    HIP_CHECK(ctx, leaf.stop(ctx->stream));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0;
-    hipEventElapsedTime(&ms, ev0, ev1);
+    HIP_CHECK(ctx, leaf.ms(&ms));
     po->leaf_ms += ms;
     po->leaf_count += ns;
     po->leaf_blocks += ns;
-    hipEventDestroy(ev0);
-    hipEventDestroy(ev1);
 
     uint32_t hist_host[66];
     HIP_CHECK(ctx, hipMemcpy(hist_host, hist.p, 66 * 4, hipMemcpyDeviceToHost));
@@ -4078,31 +4223,37 @@ static int run_storage_pass(sre_ctx *ctx, uint8_t *d_acct_roots, pass_out *po,
     if (ctx->retain_updates)
         HIP_CHECK(ctx, bhash.alloc(ns * 32));
     size_t upd_start = ctx->updates.size();
-    const uint8_t *keys =
-        (const uint8_t *)d_st + offsetof(sre_storage_entry, slot_key);
-    if (run_levels(ctx, ns, recs.as<node_rec>(), depths.as<uint8_t>(),
-                   lcp.as<int8_t>(), keys, sizeof(sre_storage_entry), hist_host, 0,
-                   seg_roots.as<uint8_t>(), nullptr, nullptr, d_err, po,
-                   ctx->retain_updates ? 1 : -1, bhash.as<uint8_t>(),
-                   0, nullptr, nullptr, 0, d_pti, n_pt, d_prows, d_prow_cnt,
-                   prow_cap, d_pti2))
+    level_in in;
+    in.n = ns;
+    in.recs = recs.as<node_rec>();
+    in.depths = depths.as<uint8_t>();
+    in.lcp = sg.lcp.as<int8_t>();
+    in.keys = (const uint8_t *)d_st + offsetof(sre_storage_entry, slot_key);
+    in.key_stride = sizeof(sre_storage_entry);
+    in.hist_host = hist_host;
+    in.seg_roots = seg_roots.as<uint8_t>();
+    in.err = d_err;
+    in.updates_kind = ctx->retain_updates ? 1 : -1;
+    in.bhash = bhash.as<uint8_t>();
+    if (run_levels(ctx, in, po, cell_capture{}, proof))
         return -1;
     if (ctx->retain_updates && ctx->updates.size() > upd_start) {
         // patch acct_key from the stashed seg ids: seg -> account index ->
         // 32-byte hashed key
         std::vector<uint32_t> seg_acct_h(n_seg);
-        HIP_CHECK(ctx, hipMemcpy(seg_acct_h.data(), seg_acct.p,
+        HIP_CHECK(ctx, hipMemcpy(seg_acct_h.data(), sg.seg_acct.p,
                                  (uint64_t)n_seg * 4, hipMemcpyDeviceToHost));
         std::vector<uint8_t> keys_h;
-        if (!d_st_in || (uint64_t)n_seg * 8 > na) {
+        // sparse incremental subset: fetch only the touched accounts' keys
+        // instead of all na x 32 B
+        bool sparse = subset && (uint64_t)n_seg * 8 <= na;
+        if (!sparse) {
             // full pass (or dense subset): strided D2H of the key column
             keys_h.resize((uint64_t)na * 32);
             HIP_CHECK(ctx, hipMemcpy2D(keys_h.data(), 32, ctx->d_acct,
                                        sizeof(sre_account_entry), 32, na,
                                        hipMemcpyDeviceToHost));
         } else {
-            // incremental subset: fetch only the touched accounts' keys
-            // instead of all na x 32 B
             keys_h.resize((uint64_t)n_seg * 32);
             for (uint32_t s2 = 0; s2 < n_seg; ++s2)
                 HIP_CHECK(ctx, hipMemcpy(keys_h.data() + 32ull * s2,
@@ -4110,37 +4261,53 @@ static int run_storage_pass(sre_ctx *ctx, uint8_t *d_acct_roots, pass_out *po,
                                              [seg_acct_h[s2]],
                                          32, hipMemcpyDeviceToHost));
         }
-        bool subset = d_st_in && (uint64_t)n_seg * 8 <= na;
         for (size_t r = upd_start; r < ctx->updates.size(); ++r) {
             sre_update_row &row = ctx->updates[r];
             uint32_t seg;
             memcpy(&seg, row.pad_, 4);
             memset(row.pad_, 0, sizeof(row.pad_));
             memcpy(row.acct_key,
-                   keys_h.data() + 32ull * (subset ? seg : seg_acct_h[seg]),
+                   keys_h.data() + 32ull * (sparse ? seg : seg_acct_h[seg]),
                    32);
         }
     }
 
-    hipLaunchKernelGGL(k_scatter_roots, dim3(grid_for(n_seg)), dim3(BLOCK), 0,
-                       ctx->stream, seg_roots.as<uint8_t>(), seg_acct.as<uint32_t>(),
-                       n_seg, d_acct_roots);
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_scatter_roots, grid_for(n_seg), BLOCK, ctx->stream,
+           seg_roots.as<uint8_t>(), sg.seg_acct.as<uint32_t>(), n_seg,
+           d_acct_roots);
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
+}
+
+// Gather the [lo[t], hi[t]) intervals of the resident storage (n_iv of
+// them; offs_host[t] = interval t's offset in the gathered array, [n_iv] =
+// the total, nonzero) into a compact array and run the subset storage pass
+// over it: fresh roots for exactly those tries, scattered into d_acct_roots.
+static int run_storage_intervals(sre_ctx *ctx, const uint32_t *d_lo,
+                                 const uint32_t *d_hi,
+                                 const std::vector<uint32_t> &offs_host,
+                                 uint8_t *d_acct_roots, pass_out *po,
+                                 uint32_t *d_err)
+{
+    uint32_t n_iv = (uint32_t)offs_host.size() - 1;
+    uint64_t total = offs_host[n_iv];
+    DBuf doffs(ctx), compact(ctx);
+    HIP_CHECK(ctx, doffs.alloc(4ull * (n_iv + 1)));
+    HIP_CHECK(ctx, hipMemcpyAsync(doffs.p, offs_host.data(), 4ull * (n_iv + 1),
+                                  hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(ctx, compact.alloc(total * sizeof(sre_storage_entry)));
+    LAUNCH(ctx, k_gather_touched, grid_for(total), BLOCK, ctx->stream, ctx->d_st,
+           d_lo, d_hi, doffs.as<uint32_t>(), n_iv, total,
+           compact.as<sre_storage_entry>());
+    return run_storage_pass(ctx, d_acct_roots, po, d_err, proof_capture{},
+                            {compact.as<sre_storage_entry>(), total});
 }
 
 static int run_account_pass(sre_ctx *ctx, const uint8_t *d_storage_roots, int subtree,
                             uint8_t *d_roots, uint8_t *d_child_refs,
                             uint8_t *d_child_lens, pass_out *po, uint32_t *d_err,
-                            int capture_depth = 0, cap_row *d_cap = nullptr,
-                            uint32_t *d_cap_cnt = nullptr,
-                            uint64_t cap_capacity = 0,
-                            const uint32_t *d_pti = nullptr, uint32_t n_pt = 0,
-                            proof_row *d_prows = nullptr,
-                            uint32_t *d_prow_cnt = nullptr,
-                            uint32_t prow_cap = 0,
-                            const uint32_t *d_pti2 = nullptr)
+                            const cell_capture &cap = {},
+                            const proof_capture &proof = {})
 {
     uint64_t na = ctx->na;
     DBuf lcp(ctx), recs(ctx), depths(ctx), hist(ctx);
@@ -4150,31 +4317,25 @@ static int run_account_pass(sre_ctx *ctx, const uint8_t *d_storage_roots, int su
     HIP_CHECK(ctx, hist.alloc(66 * 4));
     HIP_CHECK(ctx, hipMemsetAsync(hist.p, 0, 66 * 4, ctx->stream));
 
-    hipLaunchKernelGGL(k_lcp_account, dim3(grid_for(na + 1)), dim3(BLOCK), 0,
-                       ctx->stream, ctx->d_acct, na, subtree, lcp.as<int8_t>(), d_err);
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_lcp_account, grid_for(na + 1), BLOCK, ctx->stream, ctx->d_acct,
+           na, subtree, lcp.as<int8_t>(), d_err);
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (check_err(ctx, d_err))
         return -1;
 
-    hipEvent_t ev0, ev1;
-    hipEventCreate(&ev0);
-    hipEventCreate(&ev1);
-    hipEventRecord(ev0, ctx->stream);
-    hipLaunchKernelGGL(k_leaf_account, dim3(grid_for(na)), dim3(BLOCK), 0, ctx->stream,
-                       ctx->d_acct, na, d_storage_roots, lcp.as<int8_t>(), subtree,
-                       recs.as<node_rec>(), depths.as<uint8_t>(), hist.as<uint32_t>(),
-                       d_roots, d_child_refs, d_child_lens, nullptr, nullptr, nullptr, 0);
-    HIP_CHECK(ctx, hipGetLastError());
-    hipEventRecord(ev1, ctx->stream);
+    EvTimer leaf;
+    HIP_CHECK(ctx, leaf.start(ctx->stream));
+    LAUNCH(ctx, k_leaf_account, grid_for(na), BLOCK, ctx->stream, ctx->d_acct, na,
+           d_storage_roots, lcp.as<int8_t>(), subtree, recs.as<node_rec>(),
+           depths.as<uint8_t>(), hist.as<uint32_t>(), d_roots, d_child_refs,
+           d_child_lens, nullptr, nullptr, nullptr, 0);
+    HIP_CHECK(ctx, leaf.stop(ctx->stream));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0;
-    hipEventElapsedTime(&ms, ev0, ev1);
+    HIP_CHECK(ctx, leaf.ms(&ms));
     po->leaf_ms += ms;
     po->leaf_count += na;
     po->leaf_blocks += 2 * na;
-    hipEventDestroy(ev0);
-    hipEventDestroy(ev1);
 
     uint32_t hist_host[66];
     HIP_CHECK(ctx, hipMemcpy(hist_host, hist.p, 66 * 4, hipMemcpyDeviceToHost));
@@ -4183,13 +4344,22 @@ static int run_account_pass(sre_ctx *ctx, const uint8_t *d_storage_roots, int su
     if (ctx->retain_updates)
         HIP_CHECK(ctx, bhash.alloc(na * 32));
     size_t upd_start = ctx->updates.size();
-    const uint8_t *keys = (const uint8_t *)ctx->d_acct + offsetof(sre_account_entry, key);
-    if (run_levels(ctx, na, recs.as<node_rec>(), depths.as<uint8_t>(),
-                   lcp.as<int8_t>(), keys, sizeof(sre_account_entry), hist_host,
-                   subtree, d_roots, d_child_refs, d_child_lens, d_err, po,
-                   ctx->retain_updates ? 0 : -1, bhash.as<uint8_t>(),
-                   capture_depth, d_cap, d_cap_cnt, cap_capacity,
-                   d_pti, n_pt, d_prows, d_prow_cnt, prow_cap, d_pti2))
+    level_in in;
+    in.n = na;
+    in.recs = recs.as<node_rec>();
+    in.depths = depths.as<uint8_t>();
+    in.lcp = lcp.as<int8_t>();
+    in.keys = (const uint8_t *)ctx->d_acct + offsetof(sre_account_entry, key);
+    in.key_stride = sizeof(sre_account_entry);
+    in.hist_host = hist_host;
+    in.subtree = subtree;
+    in.seg_roots = d_roots;
+    in.child_refs = d_child_refs;
+    in.child_lens = d_child_lens;
+    in.err = d_err;
+    in.updates_kind = ctx->retain_updates ? 0 : -1;
+    in.bhash = bhash.as<uint8_t>();
+    if (run_levels(ctx, in, po, cap, proof))
         return -1;
     if (ctx->retain_updates) {
         for (size_t r = upd_start; r < ctx->updates.size(); ++r)
@@ -4604,8 +4774,8 @@ extern "C" int sre_account_proof(sre_ctx *ctx, const uint8_t *targets,
                                  uint64_t cap_nodes, uint32_t *out_lens,
                                  uint64_t cap_lens, uint32_t *out_counts)
 {
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
+    if (begin_call(ctx, false))
+        return -1;
     if (n_targets == 0 || n_targets > 4096) {
         set_err(ctx, "sre_account_proof: 1..4096 targets");
         return -1;
@@ -4618,8 +4788,8 @@ extern "C" int sre_account_proof(sre_ctx *ctx, const uint8_t *targets,
     uint32_t n_t = (uint32_t)n_targets;
     DBuf err(ctx), acct_roots(ctx), root(ctx), dtgt(ctx), dti(ctx), dpres(ctx),
         prows(ctx), prowc(ctx);
-    HIP_CHECK(ctx, err.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
+    if (alloc_err_flag(ctx, err))
+        return -1;
     HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
     HIP_CHECK(ctx, root.alloc(32));
     HIP_CHECK(ctx, dtgt.alloc(32ull * n_t));
@@ -4627,10 +4797,9 @@ extern "C" int sre_account_proof(sre_ctx *ctx, const uint8_t *targets,
                                   hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(ctx, dti.alloc(4ull * n_t));
     HIP_CHECK(ctx, dpres.alloc(4ull * n_t));
-    hipLaunchKernelGGL(k_proof_ti, dim3(grid_for(n_t)), dim3(BLOCK), 0,
-                       ctx->stream, ctx->d_acct, ctx->na, dtgt.as<uint8_t>(),
-                       n_t, dti.as<uint32_t>(), dpres.as<uint32_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_proof_ti, grid_for(n_t), BLOCK, ctx->stream, ctx->d_acct,
+           ctx->na, dtgt.as<uint8_t>(), n_t, dti.as<uint32_t>(),
+           dpres.as<uint32_t>());
     std::vector<uint32_t> ti(n_t), pres(n_t);
     HIP_CHECK(ctx, hipMemcpy(ti.data(), dti.p, 4ull * n_t,
                              hipMemcpyDeviceToHost));
@@ -4656,11 +4825,16 @@ extern "C" int sre_account_proof(sre_ctx *ctx, const uint8_t *targets,
     pass_out po;
     if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &po, err.as<uint32_t>()))
         return -1;
+    proof_capture proof;
+    proof.pti = dti.as<uint32_t>();
+    proof.pti2 = dti2.as<uint32_t>();
+    proof.n = n_t;
+    proof.rows = prows.as<proof_row>();
+    proof.row_count = prowc.as<uint32_t>();
+    proof.row_cap = cap_rows;
     if (run_account_pass(ctx, acct_roots.as<uint8_t>(), 0, root.as<uint8_t>(),
-                         nullptr, nullptr, &po, err.as<uint32_t>(), 0, nullptr,
-                         nullptr, 0, dti.as<uint32_t>(), n_t,
-                         prows.as<proof_row>(), prowc.as<uint32_t>(), cap_rows,
-                         dti2.as<uint32_t>()))
+                         nullptr, nullptr, &po, err.as<uint32_t>(),
+                         cell_capture{}, proof))
         return -1;
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
@@ -4782,8 +4956,8 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
                                  uint64_t cap_nodes, uint32_t *out_lens,
                                  uint64_t cap_lens, uint32_t *out_counts)
 {
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
+    if (begin_call(ctx, false))
+        return -1;
     if (ctx->na == 0 || ctx->ns == 0) {
         set_err(ctx, "sre_storage_proof: no storage resident");
         return -1;
@@ -4800,28 +4974,26 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
     }
     DBuf err(ctx), acct_roots(ctx), dtgt(ctx), dti(ctx), dpres(ctx),
         dacct(ctx), dtia(ctx), dpra(ctx), prows(ctx), prowc(ctx);
-    HIP_CHECK(ctx, err.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
+    if (alloc_err_flag(ctx, err))
+        return -1;
     HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
     HIP_CHECK(ctx, dtgt.alloc(64ull * n_t));
     HIP_CHECK(ctx, hipMemcpyAsync(dtgt.p, pairs.data(), 64ull * n_t,
                                   hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(ctx, dti.alloc(4ull * n_t));
     HIP_CHECK(ctx, dpres.alloc(4ull * n_t));
-    hipLaunchKernelGGL(k_proof_ti64, dim3(grid_for(n_t)), dim3(BLOCK), 0,
-                       ctx->stream, ctx->d_st, ctx->ns, dtgt.as<uint8_t>(),
-                       n_t, dti.as<uint32_t>(), dpres.as<uint32_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_proof_ti64, grid_for(n_t), BLOCK, ctx->stream, ctx->d_st,
+           ctx->ns, dtgt.as<uint8_t>(), n_t, dti.as<uint32_t>(),
+           dpres.as<uint32_t>());
     // account indices (for the per-target storage root)
     HIP_CHECK(ctx, dacct.alloc(32ull * n_t));
     HIP_CHECK(ctx, hipMemcpyAsync(dacct.p, acct_keys, 32ull * n_t,
                                   hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(ctx, dtia.alloc(4ull * n_t));
     HIP_CHECK(ctx, dpra.alloc(4ull * n_t));
-    hipLaunchKernelGGL(k_proof_ti, dim3(grid_for(n_t)), dim3(BLOCK), 0,
-                       ctx->stream, ctx->d_acct, ctx->na, dacct.as<uint8_t>(),
-                       n_t, dtia.as<uint32_t>(), dpra.as<uint32_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_proof_ti, grid_for(n_t), BLOCK, ctx->stream, ctx->d_acct,
+           ctx->na, dacct.as<uint8_t>(), n_t, dtia.as<uint32_t>(),
+           dpra.as<uint32_t>());
     std::vector<uint32_t> ti(n_t), pres(n_t), tia(n_t), presa(n_t);
     HIP_CHECK(ctx, hipMemcpy(ti.data(), dti.p, 4ull * n_t,
                              hipMemcpyDeviceToHost));
@@ -4850,9 +5022,15 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
     HIP_CHECK(ctx, hipMemsetAsync(prowc.p, 0, 4, ctx->stream));
 
     pass_out po;
+    proof_capture proof;
+    proof.pti = dti.as<uint32_t>();
+    proof.pti2 = dti2.as<uint32_t>();
+    proof.n = n_t;
+    proof.rows = prows.as<proof_row>();
+    proof.row_count = prowc.as<uint32_t>();
+    proof.row_cap = cap_rows;
     if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &po, err.as<uint32_t>(),
-                         dti.as<uint32_t>(), n_t, prows.as<proof_row>(),
-                         prowc.as<uint32_t>(), cap_rows, dti2.as<uint32_t>()))
+                         proof))
         return -1;
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
@@ -4964,9 +5142,8 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
 
 extern "C" int sre_root(sre_ctx *ctx, uint8_t out_root[32])
 {
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
-    memset(&ctx->stats, 0, sizeof(ctx->stats));
+    if (begin_call(ctx, true))
+        return -1;
     if (ctx->na == 0) {
         if (ctx->ns != 0) {
             set_err(ctx, "storage entries without accounts");
@@ -4975,14 +5152,12 @@ extern "C" int sre_root(sre_ctx *ctx, uint8_t out_root[32])
         memcpy(out_root, EMPTY_ROOT_H, 32);
         return 0;
     }
-    hipEvent_t t0, t1;
-    hipEventCreate(&t0);
-    hipEventCreate(&t1);
-    hipEventRecord(t0, ctx->stream);
+    EvTimer whole;
+    HIP_CHECK(ctx, whole.start(ctx->stream));
 
     DBuf err(ctx), acct_roots(ctx), root(ctx);
-    HIP_CHECK(ctx, err.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
+    if (alloc_err_flag(ctx, err))
+        return -1;
     HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
     HIP_CHECK(ctx, root.alloc(32));
 
@@ -4995,20 +5170,11 @@ extern "C" int sre_root(sre_ctx *ctx, uint8_t out_root[32])
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
 
-    hipEventRecord(t1, ctx->stream);
+    HIP_CHECK(ctx, whole.stop(ctx->stream));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     float total = 0;
-    hipEventElapsedTime(&total, t0, t1);
-    hipEventDestroy(t0);
-    hipEventDestroy(t1);
-    ctx->stats.total_ms = total;
-    ctx->stats.leaf_hash_ms = po.leaf_ms;
-    ctx->stats.leaf_count = po.leaf_count;
-    ctx->stats.leaf_blocks = po.leaf_blocks;
-    ctx->stats.branch_hash_ms = po.branch_ms;
-    ctx->stats.branch_count = po.branch_count;
-    ctx->stats.branch_blocks = po.branch_blocks;
-    ctx->stats.levels = po.levels;
+    HIP_CHECK(ctx, whole.ms(&total));
+    publish_stats(ctx, po, total);
 
     HIP_CHECK(ctx, hipMemcpy(out_root, root.p, 32, hipMemcpyDeviceToHost));
     return 0;
@@ -5016,8 +5182,8 @@ extern "C" int sre_root(sre_ctx *ctx, uint8_t out_root[32])
 
 extern "C" int sre_storage_roots(sre_ctx *ctx, uint8_t *out, uint64_t n)
 {
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
+    if (begin_call(ctx, false))
+        return -1;
     if (n != ctx->na) {
         set_err(ctx, "sre_storage_roots: n != uploaded account count");
         return -1;
@@ -5025,8 +5191,8 @@ extern "C" int sre_storage_roots(sre_ctx *ctx, uint8_t *out, uint64_t n)
     if (n == 0)
         return 0;
     DBuf err(ctx), acct_roots(ctx);
-    HIP_CHECK(ctx, err.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
+    if (alloc_err_flag(ctx, err))
+        return -1;
     HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
     pass_out po;
     if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &po, err.as<uint32_t>()))
@@ -5041,21 +5207,18 @@ extern "C" int sre_subtree_roots(sre_ctx *ctx, uint8_t out_child_refs[16][33],
                                  uint8_t out_child_lens[16],
                                  uint8_t out_root_hash[16][32], uint64_t out_counts[16])
 {
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
-    memset(&ctx->stats, 0, sizeof(ctx->stats));
+    if (begin_call(ctx, true))
+        return -1;
     memset(out_child_lens, 0, 16);
     memset(out_counts, 0, 16 * 8);
     if (ctx->na == 0)
         return 0;
-    hipEvent_t t0, t1;
-    hipEventCreate(&t0);
-    hipEventCreate(&t1);
-    hipEventRecord(t0, ctx->stream);
+    EvTimer whole;
+    HIP_CHECK(ctx, whole.start(ctx->stream));
 
     DBuf err(ctx), acct_roots(ctx), roots(ctx), crefs(ctx), clens(ctx), counts(ctx);
-    HIP_CHECK(ctx, err.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
+    if (alloc_err_flag(ctx, err))
+        return -1;
     HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
     HIP_CHECK(ctx, roots.alloc(16 * 32));
     HIP_CHECK(ctx, crefs.alloc(16 * 33));
@@ -5075,25 +5238,15 @@ extern "C" int sre_subtree_roots(sre_ctx *ctx, uint8_t out_child_refs[16][33],
                          crefs.as<uint8_t>(), clens.as<uint8_t>(), &po,
                          err.as<uint32_t>()))
         return -1;
-    hipLaunchKernelGGL(k_nibble_counts, dim3(grid_for(ctx->na)), dim3(BLOCK), 0,
-                       ctx->stream, ctx->d_acct, ctx->na, counts.as<uint64_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_nibble_counts, grid_for(ctx->na), BLOCK, ctx->stream,
+           ctx->d_acct, ctx->na, counts.as<uint64_t>());
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
-    hipEventRecord(t1, ctx->stream);
+    HIP_CHECK(ctx, whole.stop(ctx->stream));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     float total = 0;
-    hipEventElapsedTime(&total, t0, t1);
-    hipEventDestroy(t0);
-    hipEventDestroy(t1);
-    ctx->stats.total_ms = total;
-    ctx->stats.leaf_hash_ms = po.leaf_ms;
-    ctx->stats.leaf_count = po.leaf_count;
-    ctx->stats.leaf_blocks = po.leaf_blocks;
-    ctx->stats.branch_hash_ms = po.branch_ms;
-    ctx->stats.branch_count = po.branch_count;
-    ctx->stats.branch_blocks = po.branch_blocks;
-    ctx->stats.levels = po.levels;
+    HIP_CHECK(ctx, whole.ms(&total));
+    publish_stats(ctx, po, total);
 
     HIP_CHECK(ctx, hipMemcpy(out_child_refs, crefs.p, 16 * 33, hipMemcpyDeviceToHost));
     HIP_CHECK(ctx, hipMemcpy(out_child_lens, clens.p, 16, hipMemcpyDeviceToHost));
@@ -5129,9 +5282,8 @@ extern "C" int sre_finish_top(sre_ctx *ctx, const uint8_t child_refs[16][33],
     HIP_CHECK(ctx, root.alloc(32));
     HIP_CHECK(ctx, hipMemcpy(crefs.p, child_refs, 16 * 33, hipMemcpyHostToDevice));
     HIP_CHECK(ctx, hipMemcpy(clens.p, child_lens, 16, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_finish_top, dim3(1), dim3(64), 0, ctx->stream,
-                       crefs.as<uint8_t>(), clens.as<uint8_t>(), root.as<uint8_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_finish_top, 1, 64, ctx->stream, crefs.as<uint8_t>(),
+           clens.as<uint8_t>(), root.as<uint8_t>());
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     HIP_CHECK(ctx, hipMemcpy(out_root, root.p, 32, hipMemcpyDeviceToHost));
     return 0;
@@ -5232,8 +5384,8 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
     uint64_t nb = ctx->na, ns = ctx->ns;
     DBuf dl_a(ctx), dl_s(ctx), err(ctx);
     DBuf fa(ctx), fd(ctx), fdel(ctx), sa(ctx), sd(ctx), sdel(ctx);
-    HIP_CHECK(ctx, err.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
+    if (alloc_err_flag(ctx, err))
+        return -1;
     HIP_CHECK(ctx, dl_a.alloc((n_acct ? n_acct : 1) * sizeof(sre_account_delta)));
     HIP_CHECK(ctx, dl_s.alloc((n_st ? n_st : 1) * sizeof(sre_storage_entry)));
     if (n_acct)
@@ -5249,14 +5401,12 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
     HIP_CHECK(ctx, fa.alloc((nb + 1) * 4));
     HIP_CHECK(ctx, fd.alloc((n_acct + 1) * 4));
     HIP_CHECK(ctx, fdel.alloc((n_acct + 1) * 4));
-    hipLaunchKernelGGL(k_ovl_base_acct_flags, dim3(grid_for(nb + 1)), dim3(BLOCK),
-                       0, ctx->stream, ctx->d_acct, nb,
-                       dl_a.as<sre_account_delta>(), n_acct, fa.as<uint32_t>());
-    hipLaunchKernelGGL(k_ovl_delta_acct_flags, dim3(grid_for(n_acct + 1)),
-                       dim3(BLOCK), 0, ctx->stream, dl_a.as<sre_account_delta>(),
-                       n_acct, fd.as<uint32_t>(), fdel.as<uint32_t>(),
-                       err.as<uint32_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_ovl_base_acct_flags, grid_for(nb + 1), BLOCK, ctx->stream,
+           ctx->d_acct, nb, dl_a.as<sre_account_delta>(), n_acct,
+           fa.as<uint32_t>());
+    LAUNCH(ctx, k_ovl_delta_acct_flags, grid_for(n_acct + 1), BLOCK, ctx->stream,
+           dl_a.as<sre_account_delta>(), n_acct, fd.as<uint32_t>(),
+           fdel.as<uint32_t>(), err.as<uint32_t>());
     uint32_t Bk = 0, Dk = 0, Ndel = 0;
     DBuf ea(ctx), ed(ctx), edel(ctx);
     HIP_CHECK(ctx, ea.alloc((nb + 1) * 4));
@@ -5279,33 +5429,24 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
     }
     uint64_t gmax = nb > n_acct ? nb : n_acct;
     if (gmax)
-        hipLaunchKernelGGL(k_ovl_scatter_acct, dim3(grid_for(gmax)), dim3(BLOCK), 0,
-                           ctx->stream, ctx->d_acct, nb, ea.as<uint32_t>(),
-                           dl_a.as<sre_account_delta>(), n_acct, ed.as<uint32_t>(),
-                           (sre_account_entry *)new_acct);
-    HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_ovl_scatter_acct, grid_for(gmax), BLOCK, ctx->stream,
+               ctx->d_acct, nb, ea.as<uint32_t>(), dl_a.as<sre_account_delta>(),
+               n_acct, ed.as<uint32_t>(), (sre_account_entry *)new_acct);
     if (map_out) {
         HIP_CHECK(ctx, map_out->alloc((nb + 1) * 4));
-        hipLaunchKernelGGL(k_ovl_posmap, dim3(grid_for(nb + 1)), dim3(BLOCK), 0,
-                           ctx->stream, ctx->d_acct, nb, ea.as<uint32_t>(),
-                           dl_a.as<sre_account_delta>(), n_acct,
-                           ed.as<uint32_t>(), map_out->as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_ovl_posmap, grid_for(nb + 1), BLOCK, ctx->stream,
+               ctx->d_acct, nb, ea.as<uint32_t>(), dl_a.as<sre_account_delta>(),
+               n_acct, ed.as<uint32_t>(), map_out->as<uint32_t>());
     }
-    if (d_old_roots && d_new_roots && nb) {
-        hipLaunchKernelGGL(k_ovl_carry_roots, dim3(grid_for(nb)), dim3(BLOCK),
-                           0, ctx->stream, ctx->d_acct, nb, ea.as<uint32_t>(),
-                           dl_a.as<sre_account_delta>(), n_acct,
-                           ed.as<uint32_t>(), d_old_roots, d_new_roots);
-        HIP_CHECK(ctx, hipGetLastError());
-    }
+    if (d_old_roots && d_new_roots && nb)
+        LAUNCH(ctx, k_ovl_carry_roots, grid_for(nb), BLOCK, ctx->stream,
+               ctx->d_acct, nb, ea.as<uint32_t>(), dl_a.as<sre_account_delta>(),
+               n_acct, ed.as<uint32_t>(), d_old_roots, d_new_roots);
     HIP_CHECK(ctx, sdel.alloc((Ndel ? Ndel : 1) * 32));
     if (n_acct)
-        hipLaunchKernelGGL(k_ovl_gather_deleted, dim3(grid_for(n_acct)),
-                           dim3(BLOCK), 0, ctx->stream,
-                           dl_a.as<sre_account_delta>(), n_acct,
-                           edel.as<uint32_t>(), sdel.as<uint8_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_ovl_gather_deleted, grid_for(n_acct), BLOCK, ctx->stream,
+               dl_a.as<sre_account_delta>(), n_acct, edel.as<uint32_t>(),
+               sdel.as<uint8_t>());
 
     // ---- storage ----
     uint64_t new_ns = 0;
@@ -5353,23 +5494,17 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
             dwsum(ctx);
         HIP_CHECK(ctx, bpos.alloc((n_st ? n_st : 1) * 4));
         HIP_CHECK(ctx, match.alloc((n_st ? n_st : 1) * 4));
-        if (n_st) {
-            hipLaunchKernelGGL(k_sds_marks, dim3(grid_for(n_st)), dim3(BLOCK),
-                               0, ctx->stream, ctx->d_st, ns,
-                               dl_s.as<sre_storage_entry>(), n_st,
-                               bpos.as<uint32_t>(), match.as<uint32_t>());
-            HIP_CHECK(ctx, hipGetLastError());
-        }
+        if (n_st)
+            LAUNCH(ctx, k_sds_marks, grid_for(n_st), BLOCK, ctx->stream,
+                   ctx->d_st, ns, dl_s.as<sre_storage_entry>(), n_st,
+                   bpos.as<uint32_t>(), match.as<uint32_t>());
         HIP_CHECK(ctx, dwlo.alloc((Ndel ? Ndel : 1) * 4));
         HIP_CHECK(ctx, dwhi.alloc((Ndel ? Ndel : 1) * 4));
         HIP_CHECK(ctx, dwsum.alloc(((uint64_t)Ndel + 1) * 4));
-        if (Ndel) {
-            hipLaunchKernelGGL(k_sds_wipes, dim3(grid_for(Ndel)), dim3(BLOCK),
-                               0, ctx->stream, ctx->d_st, ns,
-                               sdel.as<uint8_t>(), Ndel, dwlo.as<uint32_t>(),
-                               dwhi.as<uint32_t>());
-            HIP_CHECK(ctx, hipGetLastError());
-        }
+        if (Ndel)
+            LAUNCH(ctx, k_sds_wipes, grid_for(Ndel), BLOCK, ctx->stream,
+                   ctx->d_st, ns, sdel.as<uint8_t>(), Ndel, dwlo.as<uint32_t>(),
+                   dwhi.as<uint32_t>());
         std::vector<uint32_t> bpos_h(n_st), match_h(n_st), wlo_h(Ndel),
             whi_h(Ndel), wsum_h(Ndel + 1);
         if (n_st) {
@@ -5413,42 +5548,28 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
             set_err(ctx, "apply_delta: out of memory (storage)");
             return -1;
         }
-        hipLaunchKernelGGL(k_sds_scatter, dim3(grid_for(ns)), dim3(BLOCK), 0,
-                           ctx->stream, ctx->d_st, ns,
-                           dl_s.as<sre_storage_entry>(), n_st,
-                           mex.as<uint32_t>(), eex.as<uint32_t>(),
-                           dwlo.as<uint32_t>(), dwhi.as<uint32_t>(),
-                           dwsum.as<uint32_t>(), Ndel,
-                           (sre_storage_entry *)new_st);
-        HIP_CHECK(ctx, hipGetLastError());
-        if (n_st) {
-            hipLaunchKernelGGL(k_sds_place, dim3(grid_for(n_st)), dim3(BLOCK),
-                               0, ctx->stream, dl_s.as<sre_storage_entry>(),
-                               n_st, bpos.as<uint32_t>(), mex.as<uint32_t>(),
-                               eex.as<uint32_t>(), dwlo.as<uint32_t>(),
-                               dwhi.as<uint32_t>(), dwsum.as<uint32_t>(),
-                               Ndel, (sre_storage_entry *)new_st);
-            HIP_CHECK(ctx, hipGetLastError());
-        }
+        LAUNCH(ctx, k_sds_scatter, grid_for(ns), BLOCK, ctx->stream, ctx->d_st,
+               ns, dl_s.as<sre_storage_entry>(), n_st, mex.as<uint32_t>(),
+               eex.as<uint32_t>(), dwlo.as<uint32_t>(), dwhi.as<uint32_t>(),
+               dwsum.as<uint32_t>(), Ndel, (sre_storage_entry *)new_st);
+        if (n_st)
+            LAUNCH(ctx, k_sds_place, grid_for(n_st), BLOCK, ctx->stream,
+                   dl_s.as<sre_storage_entry>(), n_st, bpos.as<uint32_t>(),
+                   mex.as<uint32_t>(), eex.as<uint32_t>(), dwlo.as<uint32_t>(),
+                   dwhi.as<uint32_t>(), dwsum.as<uint32_t>(), Ndel,
+                   (sre_storage_entry *)new_st);
         HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         st_done = true;
     }
     if (!st_done) {
         HIP_CHECK(ctx, sa.alloc((ns + 1) * 4));
         HIP_CHECK(ctx, sd.alloc((n_st + 1) * 4));
-        hipLaunchKernelGGL(k_ovl_base_st_flags, dim3(grid_for(ns + 1)),
-                           dim3(BLOCK), 0,
-                           ctx->stream, ctx->d_st, ns,
-                           dl_s.as<sre_storage_entry>(),
-                           n_st, sdel.as<uint8_t>(), (uint64_t)Ndel,
-                           sa.as<uint32_t>());
-        hipLaunchKernelGGL(k_ovl_delta_st_flags, dim3(grid_for(n_st + 1)),
-                           dim3(BLOCK),
-                           0, ctx->stream, dl_s.as<sre_storage_entry>(), n_st,
-                           sdel.as<uint8_t>(), (uint64_t)Ndel,
-                           sd.as<uint32_t>(),
-                           err.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_ovl_base_st_flags, grid_for(ns + 1), BLOCK, ctx->stream,
+               ctx->d_st, ns, dl_s.as<sre_storage_entry>(), n_st,
+               sdel.as<uint8_t>(), (uint64_t)Ndel, sa.as<uint32_t>());
+        LAUNCH(ctx, k_ovl_delta_st_flags, grid_for(n_st + 1), BLOCK, ctx->stream,
+               dl_s.as<sre_storage_entry>(), n_st, sdel.as<uint8_t>(),
+               (uint64_t)Ndel, sd.as<uint32_t>(), err.as<uint32_t>());
         uint32_t Sk = 0, Tk = 0;
         DBuf esa(ctx), esd(ctx);
         HIP_CHECK(ctx, esa.alloc((ns + 1) * 4));
@@ -5472,13 +5593,10 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
         }
         gmax = ns > n_st ? ns : n_st;
         if (gmax)
-            hipLaunchKernelGGL(k_ovl_scatter_st, dim3(grid_for(gmax)),
-                               dim3(BLOCK), 0,
-                               ctx->stream, ctx->d_st, ns, esa.as<uint32_t>(),
-                               dl_s.as<sre_storage_entry>(), n_st,
-                               esd.as<uint32_t>(),
-                               (sre_storage_entry *)new_st);
-        HIP_CHECK(ctx, hipGetLastError());
+            LAUNCH(ctx, k_ovl_scatter_st, grid_for(gmax), BLOCK, ctx->stream,
+                   ctx->d_st, ns, esa.as<uint32_t>(),
+                   dl_s.as<sre_storage_entry>(), n_st, esd.as<uint32_t>(),
+                   (sre_storage_entry *)new_st);
         HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
 
@@ -5511,39 +5629,8 @@ extern "C" int sre_apply_delta(sre_ctx *ctx,
                                uint64_t n_acct,
                                const sre_storage_entry *st_delta, uint64_t n_st)
 {
-    ctx->cells_valid = false;
-    ctx->snap_valid = false;
-    ctx->lcp_valid = false; // a plain apply invalidates cell retention
+    invalidate_retention(ctx); // a plain apply invalidates cell retention
     return apply_delta_impl(ctx, acct_delta, n_acct, st_delta, n_st, nullptr);
-}
-
-// Full root over an accounts-only state, retaining the cell-top records
-// for subsequent sre_incremental_root calls (dirty-path incremental).
-static int ensure_roots_ret(sre_ctx *ctx, uint64_t want_accounts)
-{
-    if (ctx->roots_ret_capacity >= want_accounts)
-        return 0;
-    if (ctx->d_roots_ret)
-        (void)hipFree(ctx->d_roots_ret);
-    ctx->d_roots_ret = nullptr;
-    ctx->roots_ret_capacity = 0;
-    HIP_CHECK(ctx, hipMalloc(&ctx->d_roots_ret, want_accounts * 32));
-    ctx->roots_ret_capacity = want_accounts;
-    return 0;
-}
-
-static int ensure_lcp_ret(sre_ctx *ctx, void **slot, uint64_t *cap,
-                          uint64_t want_bytes)
-{
-    if (*cap >= want_bytes)
-        return 0;
-    if (*slot)
-        (void)hipFree(*slot);
-    *slot = nullptr;
-    *cap = 0;
-    HIP_CHECK(ctx, hipMalloc(slot, want_bytes));
-    *cap = want_bytes;
-    return 0;
 }
 
 // Small-delta account merge + lcp repair (accounts-only dirty path): one
@@ -5570,11 +5657,9 @@ static int apply_delta_small(sre_ctx *ctx, const sre_account_delta *acct_delta,
                                   hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(ctx, bpos.alloc(nd * 4));
     HIP_CHECK(ctx, match.alloc(nd * 4));
-    hipLaunchKernelGGL(k_sd_marks, dim3(grid_for(nd)), dim3(BLOCK), 0,
-                       ctx->stream, ctx->d_acct, nb,
-                       dl.as<sre_account_delta>(), nd, bpos.as<uint32_t>(),
-                       match.as<uint32_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_sd_marks, grid_for(nd), BLOCK, ctx->stream, ctx->d_acct, nb,
+           dl.as<sre_account_delta>(), nd, bpos.as<uint32_t>(),
+           match.as<uint32_t>());
     std::vector<uint32_t> bpos_h(nd), match_h(nd);
     HIP_CHECK(ctx, hipMemcpy(bpos_h.data(), bpos.p, 4 * nd,
                              hipMemcpyDeviceToHost));
@@ -5600,28 +5685,22 @@ static int apply_delta_small(sre_ctx *ctx, const sre_account_delta *acct_delta,
         return -1;
     }
     HIP_CHECK(ctx, map_out->alloc((nb + 1) * 4));
-    hipLaunchKernelGGL(k_sd_scatter, dim3(grid_for(nb + 1)), dim3(BLOCK), 0,
-                       ctx->stream, ctx->d_acct, nb,
-                       dl.as<sre_account_delta>(), nd, mex.as<uint32_t>(),
-                       eex.as<uint32_t>(), (sre_account_entry *)out,
-                       map_out->as<uint32_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_sd_scatter, grid_for(nb + 1), BLOCK, ctx->stream, ctx->d_acct,
+           nb, dl.as<sre_account_delta>(), nd, mex.as<uint32_t>(),
+           eex.as<uint32_t>(), (sre_account_entry *)out,
+           map_out->as<uint32_t>());
     HIP_CHECK(ctx, npos.alloc(nd * 4));
-    hipLaunchKernelGGL(k_sd_place, dim3(grid_for(nd)), dim3(BLOCK), 0,
-                       ctx->stream, dl.as<sre_account_delta>(), nd,
-                       bpos.as<uint32_t>(), mex.as<uint32_t>(),
-                       eex.as<uint32_t>(), (sre_account_entry *)out,
-                       npos.as<uint32_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_sd_place, grid_for(nd), BLOCK, ctx->stream,
+           dl.as<sre_account_delta>(), nd, bpos.as<uint32_t>(),
+           mex.as<uint32_t>(), eex.as<uint32_t>(), (sre_account_entry *)out,
+           npos.as<uint32_t>());
     // lcp repair into the ping-pong partner
-    if (ensure_lcp_ret(ctx, &ctx->d_lcp_ret2, &ctx->lcp_ret2_capacity,
-                       new_na + 1))
+    if (grow_retained(ctx, &ctx->d_lcp_ret2, &ctx->lcp_ret2_capacity,
+                      new_na + 1))
         return -1;
-    hipLaunchKernelGGL(k_sd_lcp_copy, dim3(grid_for(nb)), dim3(BLOCK), 0,
-                       ctx->stream, map_out->as<uint32_t>(), nb,
-                       (const int8_t *)ctx->d_lcp_ret,
-                       (int8_t *)ctx->d_lcp_ret2);
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_sd_lcp_copy, grid_for(nb), BLOCK, ctx->stream,
+           map_out->as<uint32_t>(), nb, (const int8_t *)ctx->d_lcp_ret,
+           (int8_t *)ctx->d_lcp_ret2);
     std::vector<uint32_t> npos_h(nd);
     HIP_CHECK(ctx, hipMemcpy(npos_h.data(), npos.p, 4 * nd,
                              hipMemcpyDeviceToHost));
@@ -5640,14 +5719,11 @@ static int apply_delta_small(sre_ctx *ctx, const sre_account_delta *acct_delta,
     HIP_CHECK(ctx, dpatch.alloc(4 * patch.size()));
     HIP_CHECK(ctx, hipMemcpyAsync(dpatch.p, patch.data(), 4 * patch.size(),
                                   hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(ctx, err.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(k_sd_lcp_patch, dim3(grid_for(patch.size())),
-                       dim3(BLOCK), 0, ctx->stream,
-                       (const sre_account_entry *)out, new_na,
-                       dpatch.as<uint32_t>(), patch.size(),
-                       (int8_t *)ctx->d_lcp_ret2, err.as<uint32_t>());
-    HIP_CHECK(ctx, hipGetLastError());
+    if (alloc_err_flag(ctx, err))
+        return -1;
+    LAUNCH(ctx, k_sd_lcp_patch, grid_for(patch.size()), BLOCK, ctx->stream,
+           (const sre_account_entry *)out, new_na, dpatch.as<uint32_t>(),
+           patch.size(), (int8_t *)ctx->d_lcp_ret2, err.as<uint32_t>());
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
@@ -5662,24 +5738,22 @@ static int apply_delta_small(sre_ctx *ctx, const sre_account_delta *acct_delta,
     return 0;
 }
 
+// capture-row capacity for a state of na accounts
+static uint64_t cap_rows_for(uint64_t na)
+{
+    return 2 * (na < (uint64_t)N_CELLS ? na : (uint64_t)N_CELLS) + 8192;
+}
+
+// Full root, retaining the cell-top records and per-account storage roots
+// for subsequent sre_incremental_root calls (dirty-path incremental).
 extern "C" int sre_root_retaining(sre_ctx *ctx, uint8_t out_root[32])
 {
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
-    memset(&ctx->stats, 0, sizeof(ctx->stats));
-    ctx->cells_valid = false;
-    ctx->snap_valid = false;
-    ctx->lcp_valid = false;
-    uint64_t want_cap = 2 * (ctx->na < (uint64_t)N_CELLS ? ctx->na
-                                                         : (uint64_t)N_CELLS) +
-                        8192;
-    if (ctx->cap_capacity < want_cap) {
-        if (ctx->d_cap_rows)
-            (void)hipFree(ctx->d_cap_rows);
-        ctx->d_cap_rows = nullptr;
-        HIP_CHECK(ctx, hipMalloc(&ctx->d_cap_rows, want_cap * sizeof(cap_row)));
-        ctx->cap_capacity = want_cap;
-    }
+    if (begin_call(ctx, true))
+        return -1;
+    invalidate_retention(ctx);
+    if (grow_retained(ctx, &ctx->d_cap_rows, &ctx->cap_capacity,
+                      cap_rows_for(ctx->na), sizeof(cap_row)))
+        return -1;
     if (ctx->na == 0) {
         if (ctx->ns != 0) {
             set_err(ctx, "storage entries without accounts");
@@ -5690,11 +5764,12 @@ extern "C" int sre_root_retaining(sre_ctx *ctx, uint8_t out_root[32])
         memcpy(out_root, EMPTY_ROOT_H, 32);
         return 0;
     }
-    if (ensure_roots_ret(ctx, ctx->na))
+    if (grow_retained(ctx, &ctx->d_roots_ret, &ctx->roots_ret_capacity, ctx->na,
+                      32))
         return -1;
     DBuf err(ctx), roots(ctx), capcnt(ctx);
-    HIP_CHECK(ctx, err.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
+    if (alloc_err_flag(ctx, err))
+        return -1;
     HIP_CHECK(ctx, roots.alloc(32));
     HIP_CHECK(ctx, capcnt.alloc(4));
     HIP_CHECK(ctx, hipMemsetAsync(capcnt.p, 0, 4, ctx->stream));
@@ -5704,11 +5779,14 @@ extern "C" int sre_root_retaining(sre_ctx *ctx, uint8_t out_root[32])
     if (run_storage_pass(ctx, (uint8_t *)ctx->d_roots_ret, &po,
                          err.as<uint32_t>()))
         return -1;
+    cell_capture cap;
+    cap.depth = CELL_NIBBLES;
+    cap.rows = (cap_row *)ctx->d_cap_rows;
+    cap.count = capcnt.as<uint32_t>();
+    cap.capacity = ctx->cap_capacity;
     if (run_account_pass(ctx, (const uint8_t *)ctx->d_roots_ret, 0,
                          roots.as<uint8_t>(), nullptr, nullptr,
-                         &po, err.as<uint32_t>(), CELL_NIBBLES,
-                         (cap_row *)ctx->d_cap_rows, capcnt.as<uint32_t>(),
-                         ctx->cap_capacity))
+                         &po, err.as<uint32_t>(), cap))
         return -1;
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
@@ -5736,17 +5814,14 @@ static int incremental_root_impl(sre_ctx *ctx,
                                  bool with_updates,
                                  std::vector<uint8_t> *bitmap_out)
 {
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
+    if (begin_call(ctx, true))
+        return -1;
     if (!ctx->cells_valid) {
         set_err(ctx, "sre_incremental_root: needs sre_root_retaining first");
         return -1;
     }
-    memset(&ctx->stats, 0, sizeof(ctx->stats));
-    hipEvent_t t0, t1;
-    hipEventCreate(&t0);
-    hipEventCreate(&t1);
-    hipEventRecord(t0, ctx->stream);
+    EvTimer whole;
+    HIP_CHECK(ctx, whole.start(ctx->stream));
 
     // accounts-only states with accounts-only deltas skip the roots
     // machinery entirely (every storage root is EMPTY_ROOT; the leaf
@@ -5756,23 +5831,13 @@ static int incremental_root_impl(sre_ctx *ctx,
     // per-step hipMalloc at steady state), EMPTY-filled upper bound,
     // carried across the merge
     uint64_t max_na = ctx->na + n_acct;
-    if (!no_storage && ctx->roots_ret2_capacity < max_na) {
-        if (ctx->d_roots_ret2)
-            (void)hipFree(ctx->d_roots_ret2);
-        ctx->d_roots_ret2 = nullptr;
-        ctx->roots_ret2_capacity = 0;
-        HIP_CHECK(ctx, hipMalloc(&ctx->d_roots_ret2,
-                                 (max_na ? max_na : 1) * 32));
-        ctx->roots_ret2_capacity = max_na ? max_na : 1;
-    }
+    if (!no_storage && grow_retained(ctx, &ctx->d_roots_ret2,
+                                     &ctx->roots_ret2_capacity, max_na, 32))
+        return -1;
     void *new_roots = no_storage ? nullptr : ctx->d_roots_ret2;
-    if (new_roots) {
-        hipLaunchKernelGGL(k_fill_empty_roots,
-                           dim3(grid_for(max_na ? max_na : 1)), dim3(BLOCK),
-                           0, ctx->stream, (uint8_t *)new_roots,
-                           max_na ? max_na : 1);
-        HIP_CHECK(ctx, hipGetLastError());
-    }
+    if (new_roots)
+        LAUNCH(ctx, k_fill_empty_roots, grid_for(max_na ? max_na : 1), BLOCK,
+               ctx->stream, (uint8_t *)new_roots, max_na ? max_na : 1);
 
     DBuf map(ctx);
     // small accounts-only deltas take the one-pass merge with lcp repair
@@ -5800,17 +5865,15 @@ static int incremental_root_impl(sre_ctx *ctx,
     }
     uint64_t na = ctx->na;
     if (na == 0) {
-        ctx->cells_valid = false;
-    ctx->snap_valid = false;
-    ctx->lcp_valid = false;
+        invalidate_retention(ctx);
         memcpy(out_root, EMPTY_ROOT_H, 32);
         return 0;
     }
 
     DBuf err(ctx), bitmap(ctx), dl(ctx), dls(ctx), recs(ctx),
         depths(ctx), hist(ctx), roots(ctx), capcnt(ctx);
-    HIP_CHECK(ctx, err.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
+    if (alloc_err_flag(ctx, err))
+        return -1;
     HIP_CHECK(ctx, bitmap.alloc(N_CELLS));
     HIP_CHECK(ctx, hipMemsetAsync(bitmap.p, 0, N_CELLS, ctx->stream));
     HIP_CHECK(ctx, dl.alloc((n_acct ? n_acct : 1) * sizeof(sre_account_delta)));
@@ -5818,22 +5881,16 @@ static int incremental_root_impl(sre_ctx *ctx,
         HIP_CHECK(ctx, hipMemcpyAsync(dl.p, acct_delta,
                                       n_acct * sizeof(sre_account_delta),
                                       hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_mark_delta_cells, dim3(grid_for(n_acct)),
-                           dim3(BLOCK), 0, ctx->stream,
-                           dl.as<sre_account_delta>(), n_acct,
-                           bitmap.as<uint8_t>());
-        HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_mark_delta_cells, grid_for(n_acct), BLOCK, ctx->stream,
+               dl.as<sre_account_delta>(), n_acct, bitmap.as<uint8_t>());
     }
     if (n_st) {
         HIP_CHECK(ctx, dls.alloc(n_st * sizeof(sre_storage_entry)));
         HIP_CHECK(ctx, hipMemcpyAsync(dls.p, st_delta,
                                       n_st * sizeof(sre_storage_entry),
                                       hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_mark_delta_cells_st, dim3(grid_for(n_st)),
-                           dim3(BLOCK), 0, ctx->stream,
-                           dls.as<sre_storage_entry>(), n_st,
-                           bitmap.as<uint8_t>());
-        HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_mark_delta_cells_st, grid_for(n_st), BLOCK, ctx->stream,
+               dls.as<sre_storage_entry>(), n_st, bitmap.as<uint8_t>());
     }
     pass_out po;
     // recompute ONLY the touched accounts' storage tries: gather their
@@ -5855,12 +5912,10 @@ static int incremental_root_impl(sre_ctx *ctx,
         HIP_CHECK(ctx, tlo.alloc((uint64_t)nt * 4));
         HIP_CHECK(ctx, thi.alloc((uint64_t)nt * 4));
         HIP_CHECK(ctx, taidx.alloc((uint64_t)nt * 4));
-        hipLaunchKernelGGL(k_touched_bounds, dim3(grid_for(nt)), dim3(BLOCK),
-                           0, ctx->stream, ctx->d_st, ctx->ns, ctx->d_acct, na,
-                           dtk.as<uint8_t>(), nt, tlo.as<uint32_t>(),
-                           thi.as<uint32_t>(), taidx.as<uint32_t>(),
-                           (uint8_t *)new_roots, err.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_touched_bounds, grid_for(nt), BLOCK, ctx->stream,
+               ctx->d_st, ctx->ns, ctx->d_acct, na, dtk.as<uint8_t>(), nt,
+               tlo.as<uint32_t>(), thi.as<uint32_t>(), taidx.as<uint32_t>(),
+               (uint8_t *)new_roots, err.as<uint32_t>());
         std::vector<uint32_t> lo(nt), hi(nt), offs(nt + 1);
         HIP_CHECK(ctx, hipMemcpy(lo.data(), tlo.p, 4ull * nt,
                                  hipMemcpyDeviceToHost));
@@ -5869,26 +5924,11 @@ static int incremental_root_impl(sre_ctx *ctx,
         offs[0] = 0;
         for (uint32_t t = 0; t < nt; ++t)
             offs[t + 1] = offs[t] + (hi[t] - lo[t]);
-        uint64_t total = offs[nt];
-        if (total) {
-            DBuf doffs(ctx), compact(ctx);
-            HIP_CHECK(ctx, doffs.alloc(4ull * (nt + 1)));
-            HIP_CHECK(ctx, hipMemcpyAsync(doffs.p, offs.data(),
-                                          4ull * (nt + 1),
-                                          hipMemcpyHostToDevice, ctx->stream));
-            HIP_CHECK(ctx, compact.alloc(total * sizeof(sre_storage_entry)));
-            hipLaunchKernelGGL(k_gather_touched, dim3(grid_for(total)),
-                               dim3(BLOCK), 0, ctx->stream,
-                               ctx->d_st, tlo.as<uint32_t>(),
-                               thi.as<uint32_t>(), doffs.as<uint32_t>(), nt,
-                               total, compact.as<sre_storage_entry>());
-            HIP_CHECK(ctx, hipGetLastError());
-            if (run_storage_pass(ctx, (uint8_t *)new_roots, &po,
-                                 err.as<uint32_t>(), nullptr, 0, nullptr,
-                                 nullptr, 0, nullptr,
-                                 compact.as<sre_storage_entry>(), total))
-                return -1;
-        }
+        if (offs[nt] &&
+            run_storage_intervals(ctx, tlo.as<uint32_t>(), thi.as<uint32_t>(),
+                                  offs, (uint8_t *)new_roots, &po,
+                                  err.as<uint32_t>()))
+            return -1;
         if (check_err(ctx, err.as<uint32_t>()))
             return -1;
     }
@@ -5896,13 +5936,10 @@ static int incremental_root_impl(sre_ctx *ctx,
     // it already; the general path recomputes it here (arming repair for
     // the next delta)
     if (!small) {
-        if (ensure_lcp_ret(ctx, &ctx->d_lcp_ret, &ctx->lcp_ret_capacity,
-                           na + 1))
+        if (grow_retained(ctx, &ctx->d_lcp_ret, &ctx->lcp_ret_capacity, na + 1))
             return -1;
-        hipLaunchKernelGGL(k_lcp_account, dim3(grid_for(na + 1)), dim3(BLOCK),
-                           0, ctx->stream, ctx->d_acct, na, 0,
-                           (int8_t *)ctx->d_lcp_ret, err.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_lcp_account, grid_for(na + 1), BLOCK, ctx->stream,
+               ctx->d_acct, na, 0, (int8_t *)ctx->d_lcp_ret, err.as<uint32_t>());
         ctx->lcp_valid = true;
     }
     int8_t *lcp_p = (int8_t *)ctx->d_lcp_ret;
@@ -5920,21 +5957,16 @@ static int incremental_root_impl(sre_ctx *ctx,
         HIP_CHECK(ctx, abhash.alloc(na * 32));
     // seed clean cell-tops; anything invalid dirties its cell
     if (ctx->cap_count)
-        hipLaunchKernelGGL(k_revalidate_rows, dim3(grid_for(ctx->cap_count)),
-                           dim3(BLOCK), 0, ctx->stream,
-                           (const cap_row *)ctx->d_cap_rows, ctx->cap_count,
-                           map.as<uint32_t>(), lcp_p,
-                           bitmap.as<uint8_t>(), recs.as<node_rec>(),
-                           depths.as<uint8_t>(), covered.as<uint8_t>(),
-                           hist.as<uint32_t>(),
-                           with_updates ? abhash.as<uint8_t>() : nullptr);
-    HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_revalidate_rows, grid_for(ctx->cap_count), BLOCK,
+               ctx->stream, (const cap_row *)ctx->d_cap_rows, ctx->cap_count,
+               map.as<uint32_t>(), lcp_p, bitmap.as<uint8_t>(),
+               recs.as<node_rec>(), depths.as<uint8_t>(), covered.as<uint8_t>(),
+               hist.as<uint32_t>(),
+               with_updates ? abhash.as<uint8_t>() : nullptr);
     // rehash leaves of dirty cells and of positions no seed covers, with
     // the carried+patched storage roots
-    hipEvent_t ev0, ev1;
-    hipEventCreate(&ev0);
-    hipEventCreate(&ev1);
-    hipEventRecord(ev0, ctx->stream);
+    EvTimer leaf;
+    HIP_CHECK(ctx, leaf.start(ctx->stream));
     // compact the recompute set (covered == 0: dirty cells leave their
     // positions uncovered, so this is exactly dirty ∪ uncovered) and
     // launch the leaf kernel over it instead of sweeping all na lanes
@@ -5945,37 +5977,28 @@ static int incremental_root_impl(sre_ctx *ctx,
         DBuf ac(ctx), ao(ctx);
         HIP_CHECK(ctx, ac.alloc((uint64_t)nblk * 4));
         HIP_CHECK(ctx, ao.alloc((uint64_t)nblk * 4));
-        hipLaunchKernelGGL(k_active_hist, dim3(nblk), dim3(BLOCK), 0,
-                           ctx->stream, covered.as<uint8_t>(), na,
-                           ac.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_active_hist, nblk, BLOCK, ctx->stream,
+               covered.as<uint8_t>(), na, ac.as<uint32_t>());
         if (scan_u32(ctx, ac.as<uint32_t>(), ao.as<uint32_t>(), nblk,
                      &n_active))
             return -1;
         HIP_CHECK(ctx, alist.alloc(((uint64_t)n_active ? n_active : 1) * 4));
-        hipLaunchKernelGGL(k_active_scatter, dim3(nblk), dim3(BLOCK), 0,
-                           ctx->stream, covered.as<uint8_t>(), na,
-                           ao.as<uint32_t>(), alist.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_active_scatter, nblk, BLOCK, ctx->stream,
+               covered.as<uint8_t>(), na, ao.as<uint32_t>(),
+               alist.as<uint32_t>());
     }
     if (n_active)
-        hipLaunchKernelGGL(k_leaf_account, dim3(grid_for(n_active)),
-                           dim3(BLOCK), 0,
-                           ctx->stream, ctx->d_acct, na,
-                           (const uint8_t *)new_roots /* null=>EMPTY_ROOT */,
-                           lcp_p,
-                           0, recs.as<node_rec>(), depths.as<uint8_t>(),
-                           hist.as<uint32_t>(), roots.as<uint8_t>(), nullptr,
-                           nullptr, nullptr, nullptr,
-                           alist.as<uint32_t>(), n_active);
-    HIP_CHECK(ctx, hipGetLastError());
-    hipEventRecord(ev1, ctx->stream);
+        LAUNCH(ctx, k_leaf_account, grid_for(n_active), BLOCK, ctx->stream,
+               ctx->d_acct, na,
+               (const uint8_t *)new_roots /* null=>EMPTY_ROOT */, lcp_p, 0,
+               recs.as<node_rec>(), depths.as<uint8_t>(), hist.as<uint32_t>(),
+               roots.as<uint8_t>(), nullptr, nullptr, nullptr, nullptr,
+               alist.as<uint32_t>(), n_active);
+    HIP_CHECK(ctx, leaf.stop(ctx->stream));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0;
-    hipEventElapsedTime(&ms, ev0, ev1);
+    HIP_CHECK(ctx, leaf.ms(&ms));
     po.leaf_ms += ms;
-    hipEventDestroy(ev0);
-    hipEventDestroy(ev1);
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
     if (bitmap_out) { // final dirty-cell set (incl. revalidation misses)
@@ -5988,28 +6011,30 @@ static int incremental_root_impl(sre_ctx *ctx,
     // fresh capture for the next delta; the retained rows were consumed by
     // k_revalidate_rows above, so capturing over the same buffer is safe —
     // unless na grew past its capacity, in which case swap in a bigger one.
-    uint64_t want_cap = 2 * (na < (uint64_t)N_CELLS ? na : (uint64_t)N_CELLS) +
-                        8192;
-    if (ctx->cap_capacity < want_cap) {
-        void *bigger = nullptr;
-        HIP_CHECK(ctx, hipMalloc(&bigger, want_cap * sizeof(cap_row)));
-        HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->d_cap_rows);
-        ctx->d_cap_rows = bigger;
-        ctx->cap_capacity = want_cap;
-    }
+    if (grow_retained(ctx, &ctx->d_cap_rows, &ctx->cap_capacity,
+                      cap_rows_for(na), sizeof(cap_row)))
+        return -1;
     HIP_CHECK(ctx, capcnt.alloc(4));
     HIP_CHECK(ctx, hipMemsetAsync(capcnt.p, 0, 4, ctx->stream));
-    const uint8_t *keys =
-        (const uint8_t *)ctx->d_acct + offsetof(sre_account_entry, key);
     size_t upd_start = ctx->updates.size();
-    if (run_levels(ctx, na, recs.as<node_rec>(), depths.as<uint8_t>(),
-                   lcp_p, keys, sizeof(sre_account_entry), hist_host,
-                   0, roots.as<uint8_t>(), nullptr, nullptr, err.as<uint32_t>(),
-                   &po, with_updates ? 0 : -1,
-                   with_updates ? abhash.as<uint8_t>() : nullptr,
-                   CELL_NIBBLES, (cap_row *)ctx->d_cap_rows,
-                   capcnt.as<uint32_t>(), ctx->cap_capacity))
+    level_in in;
+    in.n = na;
+    in.recs = recs.as<node_rec>();
+    in.depths = depths.as<uint8_t>();
+    in.lcp = lcp_p;
+    in.keys = (const uint8_t *)ctx->d_acct + offsetof(sre_account_entry, key);
+    in.key_stride = sizeof(sre_account_entry);
+    in.hist_host = hist_host;
+    in.seg_roots = roots.as<uint8_t>();
+    in.err = err.as<uint32_t>();
+    in.updates_kind = with_updates ? 0 : -1;
+    in.bhash = with_updates ? abhash.as<uint8_t>() : nullptr;
+    cell_capture cap;
+    cap.depth = CELL_NIBBLES;
+    cap.rows = (cap_row *)ctx->d_cap_rows;
+    cap.count = capcnt.as<uint32_t>();
+    cap.capacity = ctx->cap_capacity;
+    if (run_levels(ctx, in, &po, cap))
         return -1;
     if (with_updates) // account rows carry no acct_key; clear the seg stash
         for (size_t r = upd_start; r < ctx->updates.size(); ++r)
@@ -6026,17 +6051,15 @@ static int incremental_root_impl(sre_ctx *ctx,
     }
     ctx->cells_valid = true;
 
-    hipEventRecord(t1, ctx->stream);
+    HIP_CHECK(ctx, whole.stop(ctx->stream));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     float total_ms = 0;
-    hipEventElapsedTime(&total_ms, t0, t1);
-    hipEventDestroy(t0);
-    hipEventDestroy(t1);
-    ctx->stats.total_ms = total_ms;
-    ctx->stats.leaf_hash_ms = po.leaf_ms;
-    ctx->stats.branch_hash_ms = po.branch_ms;
-    ctx->stats.branch_count = po.branch_count;
-    ctx->stats.levels = po.levels;
+    HIP_CHECK(ctx, whole.ms(&total_ms));
+    // po counts only the subset storage leaves, not the account leaves
+    // re-hashed above: the leaf/block totals would be partial numbers, so
+    // they are published as zero
+    po.leaf_count = po.leaf_blocks = po.branch_blocks = 0;
+    publish_stats(ctx, po, total_ms);
 
     HIP_CHECK(ctx, hipMemcpy(out_root, roots.p, 32, hipMemcpyDeviceToHost));
     return 0;
@@ -6228,16 +6251,11 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
                                    const sre_storage_entry *st_delta,
                                    uint64_t n_st, uint8_t out_root[32])
 {
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
-    memset(&ctx->stats, 0, sizeof(ctx->stats));
-    ctx->cells_valid = false;
-    ctx->snap_valid = false;
-    ctx->lcp_valid = false;
-    hipEvent_t t0, t1;
-    hipEventCreate(&t0);
-    hipEventCreate(&t1);
-    hipEventRecord(t0, ctx->stream);
+    if (begin_call(ctx, true))
+        return -1;
+    invalidate_retention(ctx);
+    EvTimer whole;
+    HIP_CHECK(ctx, whole.start(ctx->stream));
 
     // supplied storage roots: kind-1 path-[] rows with root_hash
     std::vector<std::array<uint8_t, 64>> kv; // key || root
@@ -6280,45 +6298,21 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
     }
 
     DBuf err(ctx), acct_roots(ctx), roots(ctx);
-    HIP_CHECK(ctx, err.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(err.p, 0, 4, ctx->stream));
+    if (alloc_err_flag(ctx, err))
+        return -1;
     HIP_CHECK(ctx, acct_roots.alloc(na * 32));
     HIP_CHECK(ctx, roots.alloc(32));
-    hipLaunchKernelGGL(k_fill_empty_roots, dim3(grid_for(na)), dim3(BLOCK),
-                       0, ctx->stream, acct_roots.as<uint8_t>(), na);
-    HIP_CHECK(ctx, hipGetLastError());
+    LAUNCH(ctx, k_fill_empty_roots, grid_for(na), BLOCK, ctx->stream,
+           acct_roots.as<uint8_t>(), na);
     pass_out po;
     if (ns) {
         // segment the resident storage; seed supplied roots / flag rebuilds
-        DBuf flags(ctx), seg_id(ctx), lcp(ctx);
-        HIP_CHECK(ctx, flags.alloc(ns * 4));
-        HIP_CHECK(ctx, seg_id.alloc(ns * 4));
-        HIP_CHECK(ctx, lcp.alloc(ns + 1));
-        hipLaunchKernelGGL(k_seg_flags_lcp, dim3(grid_for(ns + 1)),
-                           dim3(BLOCK), 0, ctx->stream, ctx->d_st, ns,
-                           flags.as<uint32_t>(), lcp.as<int8_t>(),
-                           err.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
-        uint32_t n_seg = 0;
-        if (scan_u32(ctx, flags.as<uint32_t>(), seg_id.as<uint32_t>(), ns,
-                     &n_seg))
+        storage_segs sg(ctx);
+        if (segment_storage(ctx, ctx->d_st, ns, err.as<uint32_t>(), sg))
             return -1;
-        hipLaunchKernelGGL(k_seg_fix, dim3(grid_for(ns)), dim3(BLOCK), 0,
-                           ctx->stream, flags.as<uint32_t>(),
-                           seg_id.as<uint32_t>(), ns);
-        DBuf seg_start(ctx), seg_acct(ctx), need(ctx), dkv(ctx), dtk(ctx);
-        HIP_CHECK(ctx, seg_start.alloc((uint64_t)n_seg * 4));
-        HIP_CHECK(ctx, seg_acct.alloc((uint64_t)n_seg * 4));
+        const uint32_t n_seg = sg.n_seg;
+        DBuf need(ctx), dkv(ctx), dtk(ctx);
         HIP_CHECK(ctx, need.alloc((uint64_t)n_seg * 4));
-        hipLaunchKernelGGL(k_seg_starts, dim3(grid_for(ns)), dim3(BLOCK), 0,
-                           ctx->stream, flags.as<uint32_t>(),
-                           seg_id.as<uint32_t>(), ns,
-                           seg_start.as<uint32_t>());
-        hipLaunchKernelGGL(k_seg_acct, dim3(grid_for(n_seg)), dim3(BLOCK), 0,
-                           ctx->stream, ctx->d_st, seg_start.as<uint32_t>(),
-                           n_seg, ctx->d_acct, na, seg_acct.as<uint32_t>(),
-                           err.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
         HIP_CHECK(ctx, dkv.alloc(kv.empty() ? 64 : kv.size() * 64));
         if (!kv.empty())
             HIP_CHECK(ctx, hipMemcpyAsync(dkv.p, kv.data(), kv.size() * 64,
@@ -6327,18 +6321,15 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
         if (!tkeys.empty())
             HIP_CHECK(ctx, hipMemcpyAsync(dtk.p, tkeys.data(), tkeys.size(),
                                           hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_seg_need, dim3(grid_for(n_seg)), dim3(BLOCK), 0,
-                           ctx->stream, ctx->d_st, seg_start.as<uint32_t>(),
-                           n_seg, dkv.as<uint8_t>(),
-                           (uint64_t)kv.size(), dtk.as<uint8_t>(),
-                           (uint64_t)(tkeys.size() / 32),
-                           seg_acct.as<uint32_t>(), acct_roots.as<uint8_t>(),
-                           need.as<uint32_t>());
-        HIP_CHECK(ctx, hipGetLastError());
+        LAUNCH(ctx, k_seg_need, grid_for(n_seg), BLOCK, ctx->stream, ctx->d_st,
+               sg.seg_start.as<uint32_t>(), n_seg, dkv.as<uint8_t>(),
+               (uint64_t)kv.size(), dtk.as<uint8_t>(),
+               (uint64_t)(tkeys.size() / 32), sg.seg_acct.as<uint32_t>(),
+               acct_roots.as<uint8_t>(), need.as<uint32_t>());
         std::vector<uint32_t> need_h(n_seg), start_h(n_seg);
         HIP_CHECK(ctx, hipMemcpy(need_h.data(), need.p, 4ull * n_seg,
                                  hipMemcpyDeviceToHost));
-        HIP_CHECK(ctx, hipMemcpy(start_h.data(), seg_start.p, 4ull * n_seg,
+        HIP_CHECK(ctx, hipMemcpy(start_h.data(), sg.seg_start.p, 4ull * n_seg,
                                  hipMemcpyDeviceToHost));
         std::vector<uint32_t> lo, hi, offs;
         uint64_t total = 0;
@@ -6353,28 +6344,17 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
         offs.push_back((uint32_t)total);
         if (total) {
             uint32_t nneed = (uint32_t)lo.size();
-            DBuf dlo(ctx), dhi(ctx), doffs(ctx), compact(ctx);
+            DBuf dlo(ctx), dhi(ctx);
             HIP_CHECK(ctx, dlo.alloc(4ull * nneed));
             HIP_CHECK(ctx, dhi.alloc(4ull * nneed));
-            HIP_CHECK(ctx, doffs.alloc(4ull * (nneed + 1)));
             HIP_CHECK(ctx, hipMemcpyAsync(dlo.p, lo.data(), 4ull * nneed,
                                           hipMemcpyHostToDevice, ctx->stream));
             HIP_CHECK(ctx, hipMemcpyAsync(dhi.p, hi.data(), 4ull * nneed,
                                           hipMemcpyHostToDevice, ctx->stream));
-            HIP_CHECK(ctx, hipMemcpyAsync(doffs.p, offs.data(),
-                                          4ull * (nneed + 1),
-                                          hipMemcpyHostToDevice, ctx->stream));
-            HIP_CHECK(ctx, compact.alloc(total * sizeof(sre_storage_entry)));
-            hipLaunchKernelGGL(k_gather_touched, dim3(grid_for(total)),
-                               dim3(BLOCK), 0, ctx->stream, ctx->d_st,
-                               dlo.as<uint32_t>(), dhi.as<uint32_t>(),
-                               doffs.as<uint32_t>(), nneed, total,
-                               compact.as<sre_storage_entry>());
-            HIP_CHECK(ctx, hipGetLastError());
-            if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &po,
-                                 err.as<uint32_t>(), nullptr, 0, nullptr,
-                                 nullptr, 0, nullptr,
-                                 compact.as<sre_storage_entry>(), total))
+            if (run_storage_intervals(ctx, dlo.as<uint32_t>(),
+                                      dhi.as<uint32_t>(), offs,
+                                      acct_roots.as<uint8_t>(), &po,
+                                      err.as<uint32_t>()))
                 return -1;
         }
         if (check_err(ctx, err.as<uint32_t>()))
@@ -6386,20 +6366,11 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
         return -1;
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
-    hipEventRecord(t1, ctx->stream);
+    HIP_CHECK(ctx, whole.stop(ctx->stream));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     float total_ms = 0;
-    hipEventElapsedTime(&total_ms, t0, t1);
-    hipEventDestroy(t0);
-    hipEventDestroy(t1);
-    ctx->stats.total_ms = total_ms;
-    ctx->stats.leaf_hash_ms = po.leaf_ms;
-    ctx->stats.branch_hash_ms = po.branch_ms;
-    ctx->stats.leaf_count = po.leaf_count;
-    ctx->stats.leaf_blocks = po.leaf_blocks;
-    ctx->stats.branch_count = po.branch_count;
-    ctx->stats.branch_blocks = po.branch_blocks;
-    ctx->stats.levels = po.levels;
+    HIP_CHECK(ctx, whole.ms(&total_ms));
+    publish_stats(ctx, po, total_ms);
     HIP_CHECK(ctx, hipMemcpy(out_root, roots.p, 32, hipMemcpyDeviceToHost));
     return 0;
 }
