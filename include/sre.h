@@ -336,6 +336,21 @@ const char *sre_last_error(const sre_ctx *ctx);
  * see DESIGN.md) can prove the gated path actually ran. */
 int sre_get_path_counters(sre_ctx *ctx, uint64_t out[4]);
 
+/* Read-only: what the last sre_incremental_root /
+ * sre_incremental_root_with_updates call reused and recomputed (reset on
+ * entry by the same calls that reset the path counters, so it reads all
+ * zero after any other root-type call):
+ *   out[0] retained cell-top rows examined (captured by the previous call)
+ *   out[1] rows accepted by revalidation and seeded (subtrees reused)
+ *   out[2] account leaves rehashed (dirty cells + uncovered positions)
+ *   out[3] 1 if the one-pass small account merge ran
+ *   out[4] 1 if the closed-form small-delta storage merge ran
+ *   out[5] cell-top rows captured for the next call
+ * Uncovered positions fall back to leaf recomputation and still give the
+ * right root, so the root alone cannot show that reuse happened; tests
+ * compare these with a key-only model of the cell rules. */
+int sre_get_incremental_counters(sre_ctx *ctx, uint64_t out[6]);
+
 #ifdef __cplusplus
 }
 #endif

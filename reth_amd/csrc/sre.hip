@@ -3108,6 +3108,12 @@ struct sre_ctx {
     // [2] chunks launched, [3] levels that ran the two-stream ping-pong.
     // Reset at the start of every root-type call.
     uint64_t path_cnt[4] = {0, 0, 0, 0};
+    // dirty-path reuse counters (sre_get_incremental_counters): [0] retained
+    // cell-top rows examined, [1] rows revalidated and seeded, [2] account
+    // leaves rehashed, [3] one-pass small account merge ran, [4] closed-form
+    // storage merge ran, [5] rows captured for the next call. Reset with
+    // path_cnt; filled by incremental_root_impl.
+    uint64_t inc_cnt[6] = {0, 0, 0, 0, 0, 0};
     // TrieUpdates retention (sre_root_with_updates)
     bool retain_updates = false;
     std::vector<sre_update_row> updates;
@@ -3311,6 +3317,7 @@ static int begin_call(sre_ctx *ctx, bool zero_stats)
 {
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
     memset(ctx->path_cnt, 0, sizeof(ctx->path_cnt));
+    memset(ctx->inc_cnt, 0, sizeof(ctx->inc_cnt));
     if (zero_stats)
         memset(&ctx->stats, 0, sizeof(ctx->stats));
     return 0;
@@ -5378,7 +5385,9 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
                             const uint8_t *d_old_roots = nullptr,
                             uint8_t *d_new_roots = nullptr /* carry retained
                             storage roots across the merge (new-na x 32,
-                            pre-filled EMPTY by the caller) */)
+                            pre-filled EMPTY by the caller) */,
+                            bool *st_closed_form = nullptr /* optional: set
+                            when the closed-form storage merge ran */)
 {
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
     uint64_t nb = ctx->na, ns = ctx->ns;
@@ -5560,6 +5569,8 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
                    (sre_storage_entry *)new_st);
         HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         st_done = true;
+        if (st_closed_form)
+            *st_closed_form = true;
     }
     if (!st_done) {
         HIP_CHECK(ctx, sa.alloc((ns + 1) * 4));
@@ -5822,6 +5833,7 @@ static int incremental_root_impl(sre_ctx *ctx,
     }
     EvTimer whole;
     HIP_CHECK(ctx, whole.start(ctx->stream));
+    ctx->inc_cnt[0] = ctx->cap_count;
 
     // accounts-only states with accounts-only deltas skip the roots
     // machinery entirely (every storage root is EMPTY_ROOT; the leaf
@@ -5847,6 +5859,7 @@ static int incremental_root_impl(sre_ctx *ctx,
     bool small = no_storage && n_acct > 0 && ctx->lcp_valid &&
                  (n_acct <= (ctx->na >> 6) ||
                   (getenv("SRE_SD_FORCE") && n_acct <= ctx->na));
+    bool st_closed_form = false;
     if (small) {
         if (apply_delta_small(ctx, acct_delta, n_acct, &map))
             return -1;
@@ -5859,10 +5872,12 @@ static int incremental_root_impl(sre_ctx *ctx,
                              (new_roots && ctx->ns > 0)
                                  ? (const uint8_t *)ctx->d_roots_ret
                                  : nullptr,
-                             (uint8_t *)new_roots))
+                             (uint8_t *)new_roots, &st_closed_form))
             return -1;
         ctx->lcp_valid = false; // recomputed below
     }
+    ctx->inc_cnt[3] = small;
+    ctx->inc_cnt[4] = st_closed_form;
     uint64_t na = ctx->na;
     if (na == 0) {
         invalidate_retention(ctx);
@@ -6008,6 +6023,13 @@ static int incremental_root_impl(sre_ctx *ctx,
     }
     uint32_t hist_host[66];
     HIP_CHECK(ctx, hipMemcpy(hist_host, hist.p, 66 * 4, hipMemcpyDeviceToHost));
+    // every rehashed leaf (k_leaf_account) and every seeded row
+    // (k_revalidate_rows) adds exactly one to hist
+    uint64_t level_inputs = 0;
+    for (int d = 0; d < 66; ++d)
+        level_inputs += hist_host[d];
+    ctx->inc_cnt[1] = level_inputs - n_active;
+    ctx->inc_cnt[2] = n_active;
     // fresh capture for the next delta; the retained rows were consumed by
     // k_revalidate_rows above, so capturing over the same buffer is safe —
     // unless na grew past its capacity, in which case swap in a bigger one.
@@ -6044,6 +6066,7 @@ static int incremental_root_impl(sre_ctx *ctx,
     uint32_t cnt = 0;
     HIP_CHECK(ctx, hipMemcpy(&cnt, capcnt.p, 4, hipMemcpyDeviceToHost));
     ctx->cap_count = cnt;
+    ctx->inc_cnt[5] = cnt;
     // swap the ping-pong retained roots (chained deltas)
     if (!no_storage) {
         std::swap(ctx->d_roots_ret, ctx->d_roots_ret2);
@@ -6410,5 +6433,11 @@ extern "C" int sre_get_stats(sre_ctx *ctx, sre_stats *out)
 extern "C" int sre_get_path_counters(sre_ctx *ctx, uint64_t out[4])
 {
     memcpy(out, ctx->path_cnt, sizeof(ctx->path_cnt));
+    return 0;
+}
+
+extern "C" int sre_get_incremental_counters(sre_ctx *ctx, uint64_t out[6])
+{
+    memcpy(out, ctx->inc_cnt, sizeof(ctx->inc_cnt));
     return 0;
 }

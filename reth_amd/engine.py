@@ -408,3 +408,14 @@ class StateRootEngine:
             ctypes.c_void_p(self._ctx), out))
         return {"class_levels": out[0], "fused_groups": out[1],
                 "chunks": out[2], "pipe2_levels": out[3]}
+
+    def incremental_counters(self) -> dict:
+        """What the last incremental_root / incremental_root_with_updates
+        call reused and recomputed (include/sre.h
+        sre_get_incremental_counters)."""
+        out = (ctypes.c_uint64 * 6)()
+        self._check(self._lib.sre_get_incremental_counters(
+            ctypes.c_void_p(self._ctx), out))
+        return {"examined": out[0], "seeded": out[1], "rehashed": out[2],
+                "small_acct_merge": out[3], "small_st_merge": out[4],
+                "captured": out[5]}

@@ -40,7 +40,8 @@ def test_header_parses_and_lists_expected_surface():
                  "sre_subtree_roots", "sre_finish_top", "sre_apply_delta",
                  "sre_root_retaining", "sre_incremental_root",
                  "sre_account_proof", "sre_storage_proof", "sre_get_stats",
-                 "sre_last_error", "sre_get_path_counters"]:
+                 "sre_last_error", "sre_get_path_counters",
+                 "sre_get_incremental_counters"]:
         assert must in syms, must
 
 
