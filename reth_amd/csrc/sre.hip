@@ -874,258 +874,147 @@ __device__ __forceinline__ void block_scan(uint32_t *lds, uint32_t v,
     __syncthreads();
 }
 
-// One-shot stable 66-way bucket of leaf records by parent depth, replacing
-// the per-level k_sel_count/k_sel_gather scans: every record is moved ONCE
-// into depth-major order (doff from the host-side hist prefix), after which
-// each level's fresh-leaf input is a contiguous slice. Stability (position
-// order within a depth) comes from wave-ballot ranks + per-wave LDS
-// offsets + the [depth][block] scan order. Records with depths > 65 (dead /
-// non-seeded incremental positions) are skipped.
-__global__ void k_depth_hist66(const uint8_t *__restrict__ depths, uint64_t n,
-                               uint32_t nblk, uint32_t *__restrict__ cnts)
-{
-    __shared__ uint32_t c_l[66];
-    if (threadIdx.x < 66)
-        c_l[threadIdx.x] = 0;
-    __syncthreads();
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && depths[i] <= 65)
-        atomicAdd(&c_l[depths[i]], 1u);
-    __syncthreads();
-    if (threadIdx.x < 66)
-        cnts[(uint64_t)threadIdx.x * nblk + blockIdx.x] = c_l[threadIdx.x];
-}
+// Level select over nodes kept IN PLACE: a node with interval [s, e) lives
+// at recs[s] for its whole life (leaf i at recs[i]; a branch overwrites its
+// first child's slot, k_place_nodes), and depths[s] = parent depth + 1. The
+// input of level d is then "every slot whose depth byte is d+1, in slot
+// order": one stable compaction per level, no bucket and no merges.
+//
+// Group starts fall out of the same sweep. A member at slot s starts a
+// branch group exactly when lcp[s] < d: a first child's left neighbour key
+// lies outside the branch (lcp[s] < d), every later sibling differs from
+// its predecessor's keys first at nibble d (lcp[s] == d).
+//
+// One wave sweeps LV_SPAN = 1024 slots, 16 depth bytes per lane in one
+// dwordx4 load; a wave with no member stops there. Per-wave counts are
+// scanned on the device; ranks inside a wave come from ballots, so the
+// order is stable and nothing is sorted or merged afterwards.
+#define LV_SPAN 1024u
 
-__global__ void k_depth_scatter66(const uint8_t *__restrict__ depths,
-                                  const node_rec *__restrict__ recs, uint64_t n,
-                                  uint32_t nblk,
-                                  const uint32_t *__restrict__ offs,
-                                  node_rec *__restrict__ out,
-                                  uint32_t *__restrict__ out_keys /* parallel
-                                  .s array: merge probes touch 4 B/rec
-                                  instead of 48-B-stride records */)
+// Lane's 16 slots from `base`: bit k = slot base+k is a level-d member,
+// bit 16+k = it also starts a group. Both arrays are 16-B aligned at base.
+__device__ __forceinline__ uint32_t level_masks(const uint8_t *__restrict__ depths,
+                                                const int8_t *__restrict__ lcp,
+                                                uint64_t n, uint64_t base, int d)
 {
-    __shared__ uint32_t wh[66][BLOCK / 64]; // per-wave per-depth counts
-    int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (threadIdx.x < 66)
+    if (base >= n)
+        return 0;
+    const uint32_t key = (uint32_t)(d + 1);
+    uint32_t m = 0, g = 0;
+    if (base + 16 <= n) {
+        uint4 v = *(const uint4 *)(depths + base);
+        uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int w = 0; w < BLOCK / 64; ++w)
-            wh[threadIdx.x][w] = 0;
-    __syncthreads();
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int key = (i < n) ? depths[i] : 255;
-    uint32_t rank_in_wave = 0;
-    // 66 uniform ballots: each lane keeps the rank for its own key.
-    // Fully-dead waves (all keys > 65 — the common case in incremental
-    // mode, where most positions are seeded or dead) skip the loop.
-    if (__ballot(key <= 65))
-        for (int k = 0; k < 66; ++k) {
-            uint64_t m = __ballot(key == k);
-            if (key == k)
-                rank_in_wave = __popcll(m & ((1ull << lane) - 1));
-            if (lane == 0 && m)
-                wh[k][wid] = (uint32_t)__popcll(m);
+        for (int k = 0; k < 16; ++k)
+            m |= (((w[k >> 2] >> (8 * (k & 3))) & 0xFFu) == key) ? 1u << k : 0u;
+        if (m) {
+            uint4 l = *(const uint4 *)(lcp + base);
+            uint32_t lw[4] = {l.x, l.y, l.z, l.w};
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                g |= ((int)(int8_t)(lw[k >> 2] >> (8 * (k & 3))) < d) ? 1u << k
+                                                                     : 0u;
+            g &= m;
         }
-    __syncthreads();
-    if (key > 65)
-        return;
-    uint32_t before = 0;
-    for (int w = 0; w < wid; ++w)
-        before += wh[key][w];
-    uint32_t pos = offs[(uint64_t)key * nblk + blockIdx.x] + before + rank_in_wave;
-    copy_rec(&out[pos], &recs[i]);
-    out_keys[pos] = recs[i].s;
-}
-
-
-
-// depth-major bucket of branch OUTPUT records (key = rec.depth + 1, always
-// 0..64 here; bucket 0 = segment roots, left in place and never
-// distributed). Same stable ballot-rank scheme as k_depth_scatter66.
-__global__ void k_depth_hist66_rec(const node_rec *__restrict__ recs,
-                                   uint64_t n, uint32_t nblk,
-                                   uint32_t *__restrict__ cnts)
-{
-    __shared__ uint32_t c_l[66];
-    if (threadIdx.x < 66)
-        c_l[threadIdx.x] = 0;
-    __syncthreads();
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        atomicAdd(&c_l[recs[i].depth + 1], 1u);
-    __syncthreads();
-    if (threadIdx.x < 66)
-        cnts[(uint64_t)threadIdx.x * nblk + blockIdx.x] = c_l[threadIdx.x];
-}
-
-__global__ void k_depth_scatter66_rec(const node_rec *__restrict__ recs,
-                                      uint64_t n, uint32_t nblk,
-                                      const uint32_t *__restrict__ offs,
-                                      node_rec *__restrict__ out,
-                                      uint32_t *__restrict__ out_keys)
-{
-    __shared__ uint32_t wh[66][BLOCK / 64];
-    int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (threadIdx.x < 66)
-#pragma unroll
-        for (int w = 0; w < BLOCK / 64; ++w)
-            wh[threadIdx.x][w] = 0;
-    __syncthreads();
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int key = (i < n) ? recs[i].depth + 1 : 255;
-    uint32_t rank_in_wave = 0;
-    for (int k = 0; k < 66; ++k) {
-        uint64_t m = __ballot(key == k);
-        if (key == k)
-            rank_in_wave = __popcll(m & ((1ull << lane) - 1));
-        if (lane == 0 && m)
-            wh[k][wid] = (uint32_t)__popcll(m);
+    } else { // the array's last, partial 16 slots
+        for (int k = 0; base + k < n; ++k)
+            if (depths[base + k] == key) {
+                m |= 1u << k;
+                if ((int)lcp[base + k] < d)
+                    g |= 1u << k;
+            }
     }
-    __syncthreads();
-    if (key > 65)
-        return;
-    uint32_t before = 0;
-    for (int w = 0; w < wid; ++w)
-        before += wh[key][w];
-    uint32_t pos = offs[(uint64_t)key * nblk + blockIdx.x] + before + rank_in_wave;
-    copy_rec(&out[pos], &recs[i]);
-    out_keys[pos] = recs[i].s;
+    return m | (g << 16);
 }
 
-
-
-// merge two record arrays sorted by .s (distinct keys)
-
-// Bkeys: compact 4-B .s array of B (12x denser probes than searching the
-// 48-B-stride records). Null -> probe the records directly. The block
-// computes a shared probe window from its first/last key (consecutive
-// elements' ranks are near-monotone), so per-element searches touch a
-// handful of shared cache lines instead of log2(nB) scattered ones.
-__device__ __forceinline__ uint64_t lb_s(const node_rec *B,
-                                         const uint32_t *Bkeys, uint64_t lo,
-                                         uint64_t hi, uint32_t key)
+// cnts[w] = level-d members in wave w's span, cnts[nw + w] = group starts
+// among them (two rows, scanned as one array).
+__global__ void __launch_bounds__(BLOCK) k_level_count(
+    const uint8_t *__restrict__ depths, const int8_t *__restrict__ lcp,
+    uint64_t n, int d, uint32_t nw, uint32_t *__restrict__ cnts)
 {
-    while (lo < hi) {
-        uint64_t mid = (lo + hi) / 2;
-        uint32_t bk = Bkeys ? Bkeys[mid] : B[mid].s;
-        if (bk < key)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
-__global__ void k_merge_a(const node_rec *__restrict__ A, uint64_t nA,
-                          const node_rec *__restrict__ B, uint64_t nB,
-                          node_rec *__restrict__ out,
-                          const uint32_t *__restrict__ Bkeys)
-{
-    __shared__ uint64_t wlo_s, whi_s;
-    uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x;
-    if (threadIdx.x == 0) {
-        uint64_t a = i0 < nA ? i0 : (nA ? nA - 1 : 0);
-        uint64_t b = i0 + blockDim.x - 1;
-        if (b >= nA)
-            b = nA ? nA - 1 : 0;
-        wlo_s = nA ? lb_s(B, Bkeys, 0, nB, A[a].s) : 0;
-        whi_s = nA ? lb_s(B, Bkeys, wlo_s, nB, A[b].s + 1) : 0;
-    }
-    __syncthreads();
-    uint64_t i = i0 + threadIdx.x;
-    if (i >= nA)
+    uint64_t w = ((uint64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+    int lane = threadIdx.x & 63;
+    if (w >= nw)
         return;
-    uint64_t lo = lb_s(B, Bkeys, wlo_s, whi_s, A[i].s);
-    copy_rec(&out[i + lo], &A[i]);
-}
-
-// k-way merge of sorted runs (distinct .s keys across all runs): each
-// element's output position = own index + sum of lower-bound ranks in the
-// other runs. Replaces the eager re-merge of per-depth carries: every
-// branch output is positioned exactly once, when its level is consumed.
-#define KWAY_MAX 12
-struct kway_desc {
-    const node_rec *run[KWAY_MAX];
-    const uint32_t *keys[KWAY_MAX]; // compact .s arrays (may be null)
-    uint64_t cnt[KWAY_MAX];
-    uint64_t acc[KWAY_MAX + 1]; // exclusive prefix of cnt
-    int nruns;
-};
-
-__global__ void k_merge_kway(kway_desc kd, uint64_t total,
-                             node_rec *__restrict__ out,
-                             uint32_t *__restrict__ out_keys /* nullable */)
-{
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total)
-        return;
-    int r = 0;
+    uint32_t mg = level_masks(depths, lcp, n, w * LV_SPAN + (uint64_t)lane * 16, d);
+    uint32_t c = 0; // members | starts << 16, each <= 1024
+    if (__ballot(mg != 0)) {
+        c = (uint32_t)__popc(mg & 0xFFFFu) | ((uint32_t)__popc(mg >> 16) << 16);
 #pragma unroll
-    for (int k = 1; k < KWAY_MAX; ++k)
-        if (k < kd.nruns && i >= kd.acc[k])
-            r = k;
-    uint64_t idx = i - kd.acc[r];
-    const node_rec *me = &kd.run[r][idx];
-    uint32_t key = me->s;
-    uint64_t pos = idx;
-#pragma unroll
-    for (int k = 0; k < KWAY_MAX; ++k) {
-        if (k >= kd.nruns || k == r)
+        for (int off = 32; off; off >>= 1)
+            c += __shfl_xor(c, off);
+    }
+    if (lane == 0) {
+        cnts[w] = c & 0xFFFFu;
+        cnts[(uint64_t)nw + w] = c >> 16;
+    }
+}
+
+// Gather level d's members into the dense L (slot order) and write the
+// group starts gs[]. offs = exclusive scan of k_level_count's rows, so the
+// second row's entries are offset by n_level. The span is walked in 16
+// rounds of 64 consecutive slots (lane = slot, so the record copies stay
+// coalesced); round r's member bits sit in lanes 4r..4r+3 of the masks.
+__global__ void __launch_bounds__(BLOCK) k_level_gather(
+    const uint8_t *__restrict__ depths, const int8_t *__restrict__ lcp,
+    const node_rec *__restrict__ recs, uint64_t n, int d, uint32_t nw,
+    const uint32_t *__restrict__ offs, uint32_t n_level, uint32_t n_groups,
+    node_rec *__restrict__ L, uint32_t *__restrict__ gs)
+{
+    uint64_t w = ((uint64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+    int lane = threadIdx.x & 63;
+    if (w >= nw)
+        return;
+    uint64_t base = w * LV_SPAN;
+    uint32_t mg = level_masks(depths, lcp, n, base + (uint64_t)lane * 16, d);
+    if (!__ballot(mg != 0))
+        return;
+    uint32_t pos = offs[w];
+    uint32_t gpos = offs[(uint64_t)nw + w] - n_level;
+    const uint64_t below = (1ull << lane) - 1;
+    for (int r = 0; r < 16; ++r) {
+        uint32_t v = __shfl(mg, 4 * r + (lane >> 4)) >> (lane & 15);
+        bool hit = v & 1u, start = (v >> 16) & 1u;
+        uint64_t mh = __ballot(hit);
+        if (!mh)
             continue;
-        const node_rec *B = kd.run[k];
-        const uint32_t *BK = kd.keys[k];
-        uint64_t lo = 0, hi = kd.cnt[k];
-        while (lo < hi) {
-            uint64_t mid = (lo + hi) / 2;
-            uint32_t bk = BK ? BK[mid] : B[mid].s;
-            if (bk < key)
-                lo = mid + 1;
-            else
-                hi = mid;
+        uint64_t ms = __ballot(start);
+        if (hit) {
+            uint32_t p = pos + (uint32_t)__popcll(mh & below);
+            if (p < n_level) { // always, when counts and host agree
+                copy_rec(&L[p], &recs[base + (uint64_t)r * 64 + lane]);
+                if (start) {
+                    uint32_t gp = gpos + (uint32_t)__popcll(ms & below);
+                    if (gp < n_groups)
+                        gs[gp] = p;
+                }
+            }
         }
-        pos += lo;
+        pos += (uint32_t)__popcll(mh);
+        gpos += (uint32_t)__popcll(ms);
     }
-    copy_rec(&out[pos], me);
-    if (out_keys)
-        out_keys[pos] = key;
 }
 
-__global__ void k_merge_b(const node_rec *__restrict__ A, uint64_t nA,
-                          const node_rec *__restrict__ B, uint64_t nB,
-                          node_rec *__restrict__ out,
-                          const uint32_t *__restrict__ Akeys)
+// Place level d's new nodes where the next levels look for them: record r
+// goes to recs[r.s] (its first child's slot, consumed by now) with depth
+// byte r.depth + 1. Roots (depth -1, error records included) stay out. The
+// other consumed slots keep a stale depth byte; that is harmless: a placed
+// record's byte is <= d and levels only descend, so a stale byte (d+1 or
+// more) is never selected again.
+__global__ void k_place_nodes(const node_rec *__restrict__ newn, uint32_t n_groups,
+                              uint64_t n, node_rec *__restrict__ recs,
+                              uint8_t *__restrict__ depths)
 {
-    __shared__ uint64_t wlo_s, whi_s;
-    uint64_t j0 = (uint64_t)blockIdx.x * blockDim.x;
-    if (threadIdx.x == 0) {
-        uint64_t a = j0 < nB ? j0 : (nB ? nB - 1 : 0);
-        uint64_t b = j0 + blockDim.x - 1;
-        if (b >= nB)
-            b = nB ? nB - 1 : 0;
-        wlo_s = nB ? lb_s(A, Akeys, 0, nA, B[a].s) : 0;
-        whi_s = nB ? lb_s(A, Akeys, wlo_s, nA, B[b].s + 1) : 0;
-    }
-    __syncthreads();
-    uint64_t j = j0 + threadIdx.x;
-    if (j >= nB)
+    uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_groups)
         return;
-    uint64_t lo = lb_s(A, Akeys, wlo_s, whi_s, B[j].s);
-    copy_rec(&out[j + lo], &B[j]);
-}
-
-__global__ void k_group_flags(const node_rec *__restrict__ L, uint64_t n,
-                              const int8_t *__restrict__ lcp, int d,
-                              uint32_t *__restrict__ flags)
-{
-    uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n)
+    int depth = newn[g].depth;
+    uint32_t s = newn[g].s;
+    if (depth < 0 || s >= n)
         return;
-    uint32_t f;
-    if (j == 0 || L[j].s != L[j - 1].e)
-        f = 1;
-    else
-        f = (lcp[L[j].s] < d) ? 1u : 0u;
-    flags[j] = f;
+    copy_rec(&recs[s], &newn[g]);
+    depths[s] = (uint8_t)(depth + 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -1158,17 +1047,6 @@ struct br_meta {
 };
 static_assert(sizeof(br_meta) == 20, "br_meta must be 20 bytes");
 
-// scatter group-start positions: gs[gidx[j]] = j (gs[n_groups] set by host)
-__global__ void k_group_starts(const uint32_t *__restrict__ flags,
-                               const uint32_t *__restrict__ gidx, uint64_t n,
-                               uint32_t *__restrict__ gs)
-{
-    uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n)
-        return;
-    if (flags[j])
-        gs[gidx[j]] = (uint32_t)j;
-}
 
 // Assemble one branch node per lane, streaming bytes through a register
 // appender straight into the COLUMN-MAJOR u64 scratch (no LDS at all): a
@@ -3599,37 +3477,22 @@ struct proof_capture {
     uint32_t row_cap = 0;
 };
 
-// Per-depth carry RUN LISTS: a branch node produced with parent depth p
-// waits, in place inside its level's depth-bucketed output buffer, as
-// part of a sorted run; level p consumes all its runs with ONE k-way
-// positioning merge. This replaces the eager re-merge of an
-// accumulated carry (each arrival used to re-read/rewrite the whole
-// carry); now every node is positioned exactly once. The output
-// buffers stay alive (pool-backed) until the pass ends.
-struct run_ref {
-    const node_rec *p;
-    const uint32_t *keys; // compact .s array (parallel to p)
-    uint64_t n;
-};
-
-// What run_levels carries from one level to the next.
+// What run_levels carries from one level to the next. The nodes themselves
+// wait in place (recs[s] / depths[s]); only their per-depth counts travel.
 struct level_carry {
-    std::vector<run_ref> druns[64];
-    uint64_t drun_total[64] = {0};
-    std::vector<std::unique_ptr<DBuf>> live; // buffers the runs point into
-    DBuf pend; // device counters: [p+1] nodes pending at depth p, [65] blocks
+    DBuf pend; // device counters: [p+1] nodes produced for depth p, [65] blocks
     uint32_t pending_host[66] = {0};
     explicit level_carry(sre_ctx *c) : pend(c) {}
 };
 
 // Transient buffers every level re-allocates (pool-backed, so a level
-// usually gets its predecessor's buffer back).
+// usually gets its predecessor's buffer back). lcnt/loff (the per-wave
+// select counts and their scan) are sized once per pass.
 struct level_bufs {
-    DBuf Lbuf, Cbuf, Ckeys, newn, flags, gidx, gs, scratch, meta, urows,
-        urow_cnt, urowidx;
+    DBuf Lbuf, lcnt, loff, newn, gs, scratch, meta, urows, urow_cnt, urowidx;
     explicit level_bufs(sre_ctx *c)
-        : Lbuf(c), Cbuf(c), Ckeys(c), newn(c), flags(c), gidx(c), gs(c),
-          scratch(c), meta(c), urows(c), urow_cnt(c), urowidx(c)
+        : Lbuf(c), lcnt(c), loff(c), newn(c), gs(c), scratch(c), meta(c),
+          urows(c), urow_cnt(c), urowidx(c)
     {
     }
 };
@@ -3651,146 +3514,33 @@ struct level_work {
     }
 };
 
-// Stable depth-major bucket of n records into out/out_keys (hist, scan,
-// scatter). The depth comes from d_depths[i] for the leaf records, or, when
-// d_depths is null, from the records themselves (a level's new nodes).
-static int depth_bucket(sre_ctx *ctx, const uint8_t *d_depths,
-                        const node_rec *d_recs, uint64_t n, node_rec *out,
-                        uint32_t *out_keys)
+// Level d's input and groups in one select over the in-place nodes: count
+// per wave span, scan, gather into the dense L + group starts gs. Also
+// sizes the buffers of the branch pipeline, which runs in chunks of w.chunk
+// groups so the 552-B scratch slots stay bounded. w.n_level is the host's
+// own count (leaf histogram + pending counters); the device count must
+// agree.
+static int select_level(sre_ctx *ctx, const level_in &in, level_bufs &bufs,
+                        level_work &w)
 {
-    uint32_t nblk = grid_for(n);
-    DBuf dc(ctx), do_(ctx);
-    HIP_CHECK(ctx, dc.alloc((uint64_t)66 * nblk * 4));
-    HIP_CHECK(ctx, do_.alloc((uint64_t)66 * nblk * 4));
-    if (d_depths)
-        LAUNCH(ctx, k_depth_hist66, nblk, BLOCK, ctx->stream, d_depths, n, nblk,
-               dc.as<uint32_t>());
-    else
-        LAUNCH(ctx, k_depth_hist66_rec, nblk, BLOCK, ctx->stream, d_recs, n,
-               nblk, dc.as<uint32_t>());
-    uint32_t tot = 0;
-    if (scan_u32(ctx, dc.as<uint32_t>(), do_.as<uint32_t>(), (uint64_t)66 * nblk,
-                 &tot))
+    const uint32_t nw = (uint32_t)((in.n + LV_SPAN - 1) / LV_SPAN);
+    const uint32_t grid = (nw + BLOCK / 64 - 1) / (BLOCK / 64);
+    uint32_t *cnt = bufs.lcnt.as<uint32_t>(), *off = bufs.loff.as<uint32_t>();
+    LAUNCH(ctx, k_level_count, grid, BLOCK, ctx->stream, in.depths, in.lcp, in.n,
+           w.d, nw, cnt);
+    uint32_t total = 0, n_level_dev = 0;
+    if (scan_u32(ctx, cnt, off, 2ull * nw, &total))
         return -1;
-    if (d_depths)
-        LAUNCH(ctx, k_depth_scatter66, nblk, BLOCK, ctx->stream, d_depths,
-               d_recs, n, nblk, do_.as<uint32_t>(), out, out_keys);
-    else
-        LAUNCH(ctx, k_depth_scatter66_rec, nblk, BLOCK, ctx->stream, d_recs, n,
-               nblk, do_.as<uint32_t>(), out, out_keys);
-    return 0;
-}
-
-// 2-way positioning merge of sorted runs A and B into out; a_keys/b_keys are
-// the runs' compact key arrays (null: read the records).
-static int merge_pair(sre_ctx *ctx, const node_rec *A, uint64_t nA,
-                      const uint32_t *a_keys, const node_rec *B, uint64_t nB,
-                      const uint32_t *b_keys, node_rec *out)
-{
-    LAUNCH(ctx, k_merge_a, grid_for(nA), BLOCK, ctx->stream, A, nA, B, nB, out,
-           b_keys);
-    LAUNCH(ctx, k_merge_b, grid_for(nB), BLOCK, ctx->stream, A, nA, B, nB, out,
-           a_keys);
-    return 0;
-}
-
-// Level d's input: the fresh depth-(d+1) leaf slice (nA records) merged with
-// the runs carried to depth d. The carried runs merge lazily, ONCE, k-way
-// (they are small relative to the fresh slice), then 2-way with the fresh
-// slice so the bulk elements do exactly one positioning search.
-static int merge_level_input(sre_ctx *ctx, level_carry &carry, level_bufs &bufs,
-                             int d, const node_rec *Lslice, const uint32_t *Lkeys,
-                             uint64_t nA, const node_rec **L_out)
-{
-    uint64_t nB = carry.drun_total[d];
-    const std::vector<run_ref> &runs = carry.druns[d];
-    if (nB == 0) {
-        *L_out = Lslice;
-        return 0;
-    }
-    if (nA == 0 && runs.size() == 1) {
-        *L_out = runs[0].p;
-        return 0;
-    }
-    kway_desc kd{};
-    int nr = 0;
-    for (const run_ref &rr : runs) {
-        if (nr < KWAY_MAX) {
-            kd.run[nr] = rr.p;
-            kd.keys[nr] = rr.keys;
-            kd.cnt[nr] = rr.n;
-            nr++;
-        } else {
-            // overflow run (deep tries only): pairwise-merge the
-            // two smallest resident runs to make room
-            int a = 0, b = 1;
-            if (kd.cnt[b] < kd.cnt[a])
-                std::swap(a, b);
-            for (int k = 2; k < nr; ++k) {
-                if (kd.cnt[k] < kd.cnt[a]) {
-                    b = a;
-                    a = k;
-                } else if (kd.cnt[k] < kd.cnt[b]) {
-                    b = k;
-                }
-            }
-            uint64_t tot = kd.cnt[a] + kd.cnt[b];
-            auto mb = std::make_unique<DBuf>(ctx);
-            HIP_CHECK(ctx, mb->alloc(tot * sizeof(node_rec)));
-            if (merge_pair(ctx, kd.run[a], kd.cnt[a], kd.keys[a], kd.run[b],
-                           kd.cnt[b], kd.keys[b], mb->as<node_rec>()))
-                return -1;
-            kd.run[a] = mb->as<node_rec>();
-            kd.keys[a] = nullptr;
-            kd.cnt[a] = tot;
-            carry.live.push_back(std::move(mb));
-            kd.run[b] = rr.p;
-            kd.keys[b] = rr.keys;
-            kd.cnt[b] = rr.n;
-        }
-    }
-    const node_rec *merged;
-    const uint32_t *merged_keys;
-    if (nr == 1) {
-        merged = kd.run[0];
-        merged_keys = kd.keys[0];
-    } else {
-        kd.nruns = nr;
-        kd.acc[0] = 0;
-        for (int k = 0; k < nr; ++k)
-            kd.acc[k + 1] = kd.acc[k] + kd.cnt[k];
-        HIP_CHECK(ctx, bufs.Cbuf.alloc(nB * sizeof(node_rec)));
-        HIP_CHECK(ctx, bufs.Ckeys.alloc(nB * 4));
-        LAUNCH(ctx, k_merge_kway, grid_for(nB), BLOCK, ctx->stream, kd, nB,
-               bufs.Cbuf.as<node_rec>(), bufs.Ckeys.as<uint32_t>());
-        merged = bufs.Cbuf.as<node_rec>();
-        merged_keys = bufs.Ckeys.as<uint32_t>();
-    }
-    if (nA == 0) {
-        *L_out = merged;
-        return 0;
-    }
-    HIP_CHECK(ctx, bufs.Lbuf.alloc((nA + nB) * sizeof(node_rec)));
-    if (merge_pair(ctx, Lslice, nA, Lkeys, merged, nB, merged_keys,
-                   bufs.Lbuf.as<node_rec>()))
+    HIP_CHECK(ctx, hipMemcpy(&n_level_dev, off + nw, 4, hipMemcpyDeviceToHost));
+    if (n_level_dev != w.n_level) {
+        set_err(ctx, "input/engine error: internal-group-invariant");
         return -1;
-    *L_out = bufs.Lbuf.as<node_rec>();
-    return 0;
-}
-
-// Group the level input into branch nodes (flags + scan + group starts) and
-// size the buffers of the branch pipeline, which runs in chunks of w.chunk
-// groups so the 552-B scratch slots stay bounded.
-static int find_groups(sre_ctx *ctx, const level_in &in, level_bufs &bufs,
-                       level_work &w)
-{
-    HIP_CHECK(ctx, bufs.flags.alloc(w.n_level * 4));
-    HIP_CHECK(ctx, bufs.gidx.alloc(w.n_level * 4));
-    LAUNCH(ctx, k_group_flags, grid_for(w.n_level), BLOCK, ctx->stream, w.L,
-           w.n_level, in.lcp, w.d, bufs.flags.as<uint32_t>());
-    if (scan_u32(ctx, bufs.flags.as<uint32_t>(), bufs.gidx.as<uint32_t>(),
-                 w.n_level, &w.n_groups))
-        return -1;
+    }
+    w.n_groups = total - n_level_dev;
+    w.n_level32 = n_level_dev;
+    if (bufs.Lbuf.sz < w.n_level * sizeof(node_rec))
+        HIP_CHECK(ctx, bufs.Lbuf.alloc(w.n_level * sizeof(node_rec)));
+    w.L = bufs.Lbuf.as<node_rec>();
     const uint64_t BR_CHUNK = br_chunk_groups();
     HIP_CHECK(ctx, bufs.newn.alloc((uint64_t)w.n_groups * sizeof(node_rec)));
     HIP_CHECK(ctx, bufs.gs.alloc(((uint64_t)w.n_groups + 1) * 4));
@@ -3804,10 +3554,9 @@ static int find_groups(sre_ctx *ctx, const level_in &in, level_bufs &bufs,
         HIP_CHECK(ctx, bufs.urow_cnt.alloc(4));
         HIP_CHECK(ctx, bufs.urowidx.alloc(w.chunk * 4));
     }
-    LAUNCH(ctx, k_group_starts, grid_for(w.n_level), BLOCK, ctx->stream,
-           bufs.flags.as<uint32_t>(), bufs.gidx.as<uint32_t>(), w.n_level,
-           bufs.gs.as<uint32_t>());
-    w.n_level32 = (uint32_t)w.n_level;
+    LAUNCH(ctx, k_level_gather, grid, BLOCK, ctx->stream, in.depths, in.lcp,
+           in.recs, in.n, w.d, nw, off, n_level_dev, w.n_groups,
+           bufs.Lbuf.as<node_rec>(), bufs.gs.as<uint32_t>());
     HIP_CHECK(ctx, hipMemcpyAsync(bufs.gs.as<uint32_t>() + w.n_groups,
                                   &w.n_level32, 4, hipMemcpyHostToDevice,
                                   ctx->stream));
@@ -3985,55 +3734,14 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
     return 0;
 }
 
-// Distribute level d's new nodes into their target per-depth carries.
-// pend[p+1] - previous snapshot = nodes newly pending at depth p.
-static int distribute_new_nodes(sre_ctx *ctx, level_carry &carry,
-                                level_bufs &bufs, int d, uint32_t n_groups,
-                                uint64_t *branch_blocks)
+// Put level d's new nodes in place for the levels that wait for them (queued
+// behind the branch chunks; the caller synchronises).
+static int place_new_nodes(sre_ctx *ctx, const level_in &in, level_bufs &bufs,
+                           uint32_t n_groups)
 {
-    uint32_t *pending_host = carry.pending_host;
-    uint32_t prev_pending[66];
-    memcpy(prev_pending, pending_host, sizeof(prev_pending));
-    HIP_CHECK(ctx, hipMemcpy(pending_host, carry.pend.p, 66 * 4,
-                             hipMemcpyDeviceToHost));
-    pending_host[d + 1] = 0; // consumed (and d's carry was emptied)
-    HIP_CHECK(ctx, hipMemsetAsync((uint8_t *)carry.pend.p + 4 * (d + 1), 0, 4,
-                                  ctx->stream));
-    *branch_blocks = pending_host[65];
-    // one stable depth-major scatter of the outputs; per-depth slices
-    // then wait in place as carried runs — no per-depth rescans.
-    uint64_t fresh_cnt[64] = {0};
-    uint64_t slice_off[66];
-    bool any_fresh = false;
-    uint64_t roots_n = n_groups;
-    for (int p = 0; p < d; ++p) {
-        fresh_cnt[p] = pending_host[p + 1] - prev_pending[p + 1];
-        roots_n -= fresh_cnt[p];
-        any_fresh |= fresh_cnt[p] != 0;
-    }
-    slice_off[0] = 0;
-    slice_off[1] = roots_n; // bucket 0: segment roots, stay put
-    for (int v = 1; v < 65; ++v)
-        slice_off[v + 1] = slice_off[v] + (v - 1 < d ? fresh_cnt[v - 1] : 0);
-    if (!any_fresh)
-        return 0;
-    auto nb = std::make_unique<DBuf>(ctx);
-    auto nbk = std::make_unique<DBuf>(ctx);
-    HIP_CHECK(ctx, nb->alloc((uint64_t)n_groups * sizeof(node_rec)));
-    HIP_CHECK(ctx, nbk->alloc((uint64_t)n_groups * 4));
-    if (depth_bucket(ctx, nullptr, bufs.newn.as<node_rec>(), n_groups,
-                     nb->as<node_rec>(), nbk->as<uint32_t>()))
-        return -1;
-    // record the per-depth slices as carried runs, in place
-    for (int p = 0; p < d; ++p)
-        if (fresh_cnt[p]) {
-            carry.druns[p].push_back({nb->as<node_rec>() + slice_off[p + 1],
-                                      nbk->as<uint32_t>() + slice_off[p + 1],
-                                      fresh_cnt[p]});
-            carry.drun_total[p] += fresh_cnt[p];
-        }
-    carry.live.push_back(std::move(nb));
-    carry.live.push_back(std::move(nbk));
+    if (n_groups)
+        LAUNCH(ctx, k_place_nodes, grid_for(n_groups), BLOCK, ctx->stream,
+               bufs.newn.as<node_rec>(), n_groups, in.n, in.recs, in.depths);
     return 0;
 }
 
@@ -4055,43 +3763,31 @@ static int run_levels(sre_ctx *ctx, const level_in &in, pass_out *po,
     level_bufs bufs(ctx);
     HIP_CHECK(ctx, carry.pend.alloc(66 * 4));
     HIP_CHECK(ctx, hipMemsetAsync(carry.pend.p, 0, 66 * 4, ctx->stream));
+    const uint64_t nw = (in.n + LV_SPAN - 1) / LV_SPAN;
+    HIP_CHECK(ctx, bufs.lcnt.alloc(2 * nw * 4));
+    HIP_CHECK(ctx, bufs.loff.alloc(2 * nw * 4));
     uint64_t branch_blocks_base = po->branch_blocks;
     EvTimer timer;
 
-    // (once) stable depth-major bucket of the leaf records: doff[v] =
-    // start of the depth-v slice; every level's fresh input is then a slice.
-    DBuf dsorted(ctx), dskeys(ctx);
-    uint64_t doff[67];
-    HIP_CHECK(ctx, dsorted.alloc(in.n * sizeof(node_rec)));
-    HIP_CHECK(ctx, dskeys.alloc(in.n * 4));
-    if (depth_bucket(ctx, in.depths, in.recs, in.n, dsorted.as<node_rec>(),
-                     dskeys.as<uint32_t>()))
-        return -1;
-    doff[0] = 0;
-    for (int v = 0; v < 66; ++v)
-        doff[v + 1] = doff[v] + hist_host[v];
-
     for (int d = maxd; d >= 0; --d) {
-        uint64_t nA = hist_host[d + 1];
-        if (nA == 0 && carry.drun_total[d] == 0)
+        // fresh leaves of depth d plus the branches placed for depth d
+        uint64_t n_level = (uint64_t)hist_host[d + 1] + carry.pending_host[d + 1];
+        if (n_level == 0)
             continue;
         po->levels++;
         level_work w(ctx);
         w.d = d;
-        w.n_level = nA + carry.drun_total[d];
-        // fresh leaves (the depth-(d+1) slice of dsorted) + carried runs
-        if (merge_level_input(ctx, carry, bufs, d,
-                              dsorted.as<node_rec>() + doff[d + 1],
-                              dskeys.as<uint32_t>() + doff[d + 1], nA, &w.L))
+        w.n_level = n_level;
+        if (select_level(ctx, in, bufs, w))
             return -1;
         if (cap.depth > 0 && d == cap.depth - 1)
             LAUNCH(ctx, k_capture_L, grid_for(w.n_level), BLOCK, ctx->stream,
                    w.L, w.n_level, in.keys, in.key_stride, cap.rows, cap.count,
                    cap.capacity, in.err,
                    in.updates_kind >= 0 ? in.bhash : nullptr);
-        if (find_groups(ctx, in, bufs, w) ||
-            partition_classes(ctx, in, proof.n, bufs, w) ||
-            run_branch_chunks(ctx, in, proof, carry, bufs, w, timer))
+        if (partition_classes(ctx, in, proof.n, bufs, w) ||
+            run_branch_chunks(ctx, in, proof, carry, bufs, w, timer) ||
+            place_new_nodes(ctx, in, bufs, w.n_groups))
             return -1;
         HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         float ms = 0;
@@ -4099,20 +3795,13 @@ static int run_levels(sre_ctx *ctx, const level_in &in, pass_out *po,
         po->branch_ms += ms;
         po->branch_count += w.n_groups;
 
-        // this level's inputs are consumed (slices stay in their live
-        // buffers; freed when the pass ends)
-        carry.druns[d].clear();
-        carry.drun_total[d] = 0;
-        uint64_t blocks = 0;
-        if (distribute_new_nodes(ctx, carry, bufs, d, w.n_groups, &blocks))
-            return -1;
-        po->branch_blocks = branch_blocks_base + blocks;
+        // pend[p+1] = nodes produced so far for depth p (complete for every
+        // p the loop has yet to reach: parents lie strictly above), [65] =
+        // keccak blocks
+        HIP_CHECK(ctx, hipMemcpy(carry.pending_host, carry.pend.p, 66 * 4,
+                                 hipMemcpyDeviceToHost));
+        po->branch_blocks = branch_blocks_base + carry.pending_host[65];
     }
-    for (int p = 0; p < 64; ++p)
-        if (carry.drun_total[p] != 0) {
-            set_err(ctx, "internal: carry not empty after level 0");
-            return -1;
-        }
     return 0;
 }
 
@@ -4222,6 +3911,10 @@ static int run_storage_pass(sre_ctx *ctx, uint8_t *d_acct_roots, pass_out *po,
     po->leaf_ms += ms;
     po->leaf_count += ns;
     po->leaf_blocks += ns;
+    // a rejected entry (zero-valued slot) wrote neither record nor depth
+    // byte: stop before any level selects over unwritten slots
+    if (check_err(ctx, d_err))
+        return -1;
 
     uint32_t hist_host[66];
     HIP_CHECK(ctx, hipMemcpy(hist_host, hist.p, 66 * 4, hipMemcpyDeviceToHost));
@@ -4343,6 +4036,9 @@ static int run_account_pass(sre_ctx *ctx, const uint8_t *d_storage_roots, int su
     po->leaf_ms += ms;
     po->leaf_count += na;
     po->leaf_blocks += 2 * na;
+    // as in the storage pass: no level runs once an error is flagged
+    if (check_err(ctx, d_err))
+        return -1;
 
     uint32_t hist_host[66];
     HIP_CHECK(ctx, hipMemcpy(hist_host, hist.p, 66 * 4, hipMemcpyDeviceToHost));
