@@ -107,6 +107,39 @@ __device__ __forceinline__ uint64_t rotl64c(uint64_t x, int n)
     return ((uint64_t)nh << 32) | nl;
 }
 
+// 3-input bitwise ops on 64-bit lanes. gfx950 has v_bitop3_b32 (any boolean
+// function of three operands, truth table in the immediate: src0 = 0xF0,
+// src1 = 0xCC, src2 = 0xAA); the compiler does not form it from the plain
+// expression (it emits v_bfi + v_xor for chi), so it is asked for by name.
+__device__ __forceinline__ uint64_t xor3_64(uint64_t a, uint64_t b, uint64_t c)
+{
+#if defined(__gfx950__)
+    uint32_t lo = __builtin_amdgcn_bitop3_b32((uint32_t)a, (uint32_t)b,
+                                              (uint32_t)c, 0x96);
+    uint32_t hi = __builtin_amdgcn_bitop3_b32((uint32_t)(a >> 32),
+                                              (uint32_t)(b >> 32),
+                                              (uint32_t)(c >> 32), 0x96);
+    return ((uint64_t)hi << 32) | lo;
+#else
+    return a ^ b ^ c;
+#endif
+}
+
+// chi: a ^ (~b & c), truth table 0xF0 ^ (~0xCC & 0xAA) = 0xD2
+__device__ __forceinline__ uint64_t chi64(uint64_t a, uint64_t b, uint64_t c)
+{
+#if defined(__gfx950__)
+    uint32_t lo = __builtin_amdgcn_bitop3_b32((uint32_t)a, (uint32_t)b,
+                                              (uint32_t)c, 0xD2);
+    uint32_t hi = __builtin_amdgcn_bitop3_b32((uint32_t)(a >> 32),
+                                              (uint32_t)(b >> 32),
+                                              (uint32_t)(c >> 32), 0xD2);
+    return ((uint64_t)hi << 32) | lo;
+#else
+    return a ^ (~b & c);
+#endif
+}
+
 // Keccak-f[1600]. Inner loops unrolled so every s[]/b[] index is a
 // compile-time constant (register-resident; dynamic indexing would spill to
 // scratch — cdna_hip_programming.md §5.4 rule 20).
@@ -118,22 +151,26 @@ __device__ void keccak_f(uint64_t s[25])
     // rho+pi as the XKCP in-place cycle walk (one temp, no b[25] copy —
     // the copy cost ~15 v_mov_b64 per round) and chi row-wise in place
     // with two saved lanes. Validated bit-exact against FIPS-202 vectors.
+    // Theta and chi run on 3-input ops: column parity as two xor3, the
+    // theta update s ^= c[x-1] ^ rotl(c[x+1],1) as one xor3 per lane (no
+    // d[] array), chi as one op per lane.
     constexpr int PILN[24] = {10, 7,  11, 17, 18, 3, 5,  16, 8,  21, 24, 4,
                               15, 23, 19, 13, 12, 2, 20, 14, 22, 9,  6,  1};
     constexpr int ROTC[24] = {1,  3,  6,  10, 15, 21, 28, 36, 45, 55, 2,  14,
                               27, 41, 56, 8,  25, 43, 62, 18, 39, 61, 20, 44};
 #pragma unroll KECCAK_UNROLL
     for (int r = 0; r < 24; ++r) {
-        uint64_t c[5], d[5];
+        uint64_t c[5], cr[5];
 #pragma unroll
         for (int x = 0; x < 5; ++x)
-            c[x] = s[x] ^ s[x + 5] ^ s[x + 10] ^ s[x + 15] ^ s[x + 20];
+            c[x] = xor3_64(xor3_64(s[x], s[x + 5], s[x + 10]), s[x + 15],
+                           s[x + 20]);
 #pragma unroll
         for (int x = 0; x < 5; ++x)
-            d[x] = c[(x + 4) % 5] ^ rotl64c(c[(x + 1) % 5], 1);
+            cr[x] = rotl64c(c[x], 1);
 #pragma unroll
         for (int i = 0; i < 25; ++i)
-            s[i] ^= d[i % 5];
+            s[i] = xor3_64(s[i], c[(i + 4) % 5], cr[(i + 1) % 5]);
         uint64_t t = s[1], u;
 #pragma unroll
         for (int k = 0; k < 24; ++k) {
@@ -145,11 +182,11 @@ __device__ void keccak_f(uint64_t s[25])
 #pragma unroll
         for (int y = 0; y < 25; y += 5) {
             uint64_t a0 = s[y], a1 = s[y + 1];
-            s[y] ^= (~a1) & s[y + 2];
-            s[y + 1] ^= (~s[y + 2]) & s[y + 3];
-            s[y + 2] ^= (~s[y + 3]) & s[y + 4];
-            s[y + 3] ^= (~s[y + 4]) & a0;
-            s[y + 4] ^= (~a0) & a1;
+            s[y] = chi64(s[y], a1, s[y + 2]);
+            s[y + 1] = chi64(s[y + 1], s[y + 2], s[y + 3]);
+            s[y + 2] = chi64(s[y + 2], s[y + 3], s[y + 4]);
+            s[y + 3] = chi64(s[y + 3], s[y + 4], a0);
+            s[y + 4] = chi64(s[y + 4], a0, a1);
         }
         s[0] ^= KRC[r];
     }
@@ -367,6 +404,44 @@ __global__ void __launch_bounds__(BLOCK) k_keccak_batch(
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         o[k] = hash[k];
+}
+
+// Any message length: blocks are absorbed straight from global memory, byte
+// by byte, with the pad bytes patched in (no LDS slot, so no length limit).
+// The multi-block sibling of k_keccak_batch; same keccak_f.
+__global__ void __launch_bounds__(BLOCK) k_keccak_long(
+    const uint8_t *__restrict__ in, uint64_t stride, uint32_t len, uint64_t n,
+    uint8_t *__restrict__ out)
+{
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint8_t *msg = in + i * stride;
+    const uint32_t nblocks = len / 136 + 1, last = nblocks * 136 - 1;
+    uint64_t s[25];
+#pragma unroll
+    for (int k = 0; k < 25; ++k)
+        s[k] = 0;
+    for (uint32_t blk = 0; blk < nblocks; ++blk) {
+#pragma unroll
+        for (int w = 0; w < 17; ++w) {
+            uint64_t v = 0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                uint32_t b = blk * 136 + w * 8 + k;
+                uint8_t c = b < len ? msg[b] : (b == len ? 0x01 : 0x00);
+                if (b == last)
+                    c |= 0x80;
+                v |= (uint64_t)c << (8 * k);
+            }
+            s[w] ^= v;
+        }
+        keccak_f(s);
+    }
+    uint64_t *o = (uint64_t *)(out + 32 * i);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        o[k] = s[k];
 }
 
 // ---------------------------------------------------------------------------
@@ -876,7 +951,7 @@ __device__ __forceinline__ void block_scan(uint32_t *lds, uint32_t v,
 
 // Level select over nodes kept IN PLACE: a node with interval [s, e) lives
 // at recs[s] for its whole life (leaf i at recs[i]; a branch overwrites its
-// first child's slot, k_place_nodes), and depths[s] = parent depth + 1. The
+// first child's slot, branch_tail), and depths[s] = parent depth + 1. The
 // input of level d is then "every slot whose depth byte is d+1, in slot
 // order": one stable compaction per level, no bucket and no merges.
 //
@@ -994,27 +1069,6 @@ __global__ void __launch_bounds__(BLOCK) k_level_gather(
         pos += (uint32_t)__popcll(mh);
         gpos += (uint32_t)__popcll(ms);
     }
-}
-
-// Place level d's new nodes where the next levels look for them: record r
-// goes to recs[r.s] (its first child's slot, consumed by now) with depth
-// byte r.depth + 1. Roots (depth -1, error records included) stay out. The
-// other consumed slots keep a stale depth byte; that is harmless: a placed
-// record's byte is <= d and levels only descend, so a stale byte (d+1 or
-// more) is never selected again.
-__global__ void k_place_nodes(const node_rec *__restrict__ newn, uint32_t n_groups,
-                              uint64_t n, node_rec *__restrict__ recs,
-                              uint8_t *__restrict__ depths)
-{
-    uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_groups)
-        return;
-    int depth = newn[g].depth;
-    uint32_t s = newn[g].s;
-    if (depth < 0 || s >= n)
-        return;
-    copy_rec(&recs[s], &newn[g]);
-    depths[s] = (uint8_t)(depth + 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -1318,6 +1372,13 @@ __global__ void __launch_bounds__(BLOCK_A) k_branch_assemble(
 // Everything after a branch's RLP keccak: ref composition, extension/root
 // wraps, record/bhash/seg-root emission and the pending-histogram bumps.
 // Shared by the split hash kernel and the fused 1-block kernel.
+// A non-root node is placed where the next levels look for it: recs[mt.s]
+// (its first child's slot, consumed by now: this level reads the dense copy
+// L, never recs, and every group has its own s) with depth byte P + 1.
+// Roots and error groups store no record. The other consumed slots keep a
+// stale depth byte; that is harmless: a placed record's byte is <= d and
+// levels only descend, so a stale byte (d+1 or more) is never selected
+// again.
 // `inline_src64` points at the branch RLP's word 0 for the <32-B inline
 // case, with `inline_stride` u64s between message words (column-major
 // scratch: stride = chunk; LDS row: stride = 1). `ext` is a per-lane LDS
@@ -1327,9 +1388,10 @@ __global__ void __launch_bounds__(BLOCK_A) k_branch_assemble(
 __device__ __forceinline__ void branch_tail(
     const br_meta &mt, int subtree, const uint8_t *keys, uint64_t key_stride,
     const uint64_t br_hash[4], const uint64_t *inline_src64,
-    uint64_t inline_stride, uint8_t *ext, node_rec *r, uint8_t *seg_roots,
-    uint8_t *child_refs, uint8_t *child_lens, uint32_t *hist_l,
-    uint8_t *bhash_by_s, sre_update_row *urows, uint32_t urowidx_val)
+    uint64_t inline_stride, uint8_t *ext, node_rec *recs, uint8_t *depths,
+    uint64_t n, uint8_t *seg_roots, uint8_t *child_refs, uint8_t *child_lens,
+    uint32_t *hist_l, uint8_t *bhash_by_s, sre_update_row *urows,
+    uint32_t urowidx_val)
 {
     int d = mt.d;
     int kblocks = mt.br_len / 136 + 1;
@@ -1429,26 +1491,23 @@ __device__ __forceinline__ void branch_tail(
         // whole 48-B record composed in registers, 3 x dwordx4 stores
         uint32_t w3 = (uint32_t)(uint8_t)(int8_t)mt.P | ((uint32_t)wrl << 8) |
                       ((uint32_t)(wrefw[0] & 0xFFFF) << 16);
-        uint4 *r4 = (uint4 *)r;
-        r4[0] = make_uint4(mt.s, mt.e, mt.seg, w3);
-        r4[1] = make_uint4((uint32_t)(wrefw[0] >> 16),
-                           (uint32_t)((wrefw[0] >> 48) | (wrefw[1] << 16)),
-                           (uint32_t)(wrefw[1] >> 16),
-                           (uint32_t)((wrefw[1] >> 48) | (wrefw[2] << 16)));
-        r4[2] = make_uint4((uint32_t)(wrefw[2] >> 16),
-                           (uint32_t)((wrefw[2] >> 48) | (wrefw[3] << 16)),
-                           (uint32_t)(wrefw[3] >> 16),
-                           (uint32_t)((wrefw[3] >> 48) & 0xFFFF) |
-                               ((uint32_t)(wrefw[4] & 0xFF) << 16) |
-                               ((uint32_t)pb << 24));
+        if (mt.s < n) {
+            uint4 *r4 = (uint4 *)&recs[mt.s];
+            r4[0] = make_uint4(mt.s, mt.e, mt.seg, w3);
+            r4[1] = make_uint4((uint32_t)(wrefw[0] >> 16),
+                               (uint32_t)((wrefw[0] >> 48) | (wrefw[1] << 16)),
+                               (uint32_t)(wrefw[1] >> 16),
+                               (uint32_t)((wrefw[1] >> 48) | (wrefw[2] << 16)));
+            r4[2] = make_uint4((uint32_t)(wrefw[2] >> 16),
+                               (uint32_t)((wrefw[2] >> 48) | (wrefw[3] << 16)),
+                               (uint32_t)(wrefw[3] >> 16),
+                               (uint32_t)((wrefw[3] >> 48) & 0xFFFF) |
+                                   ((uint32_t)(wrefw[4] & 0xFF) << 16) |
+                                   ((uint32_t)pb << 24));
+            depths[mt.s] = (uint8_t)(mt.P + 1);
+        }
         atomicAdd(&hist_l[mt.P + 1], 1u);
     } else {
-        r->s = mt.s;
-        r->e = mt.e;
-        r->seg = mt.seg;
-        r->pad_ = 0;
-        r->depth = -1;
-        r->ref_len = 0;
         if (subtree) {
             wrap(1);
             uint8_t *cr = child_refs + 33ull * mt.seg;
@@ -1470,8 +1529,8 @@ __global__ void __launch_bounds__(BLOCK) k_branch_hash(
     const uint8_t *__restrict__ scratch, uint64_t scratch_stride,
     const br_meta *__restrict__ meta,
     uint32_t n_groups, const uint8_t *__restrict__ keys, uint64_t key_stride,
-    int subtree, node_rec *__restrict__ out, const uint32_t *__restrict__ perm,
-    uint8_t *__restrict__ seg_roots,
+    int subtree, node_rec *__restrict__ recs, uint8_t *__restrict__ depths,
+    uint64_t n, uint8_t *__restrict__ seg_roots,
     uint8_t *__restrict__ child_refs, uint8_t *__restrict__ child_lens,
     uint32_t *__restrict__ pending, uint32_t *__restrict__ err,
     uint8_t *__restrict__ bhash_by_s, /* updates mode: branch hash by
@@ -1490,19 +1549,10 @@ __global__ void __launch_bounds__(BLOCK) k_branch_hash(
     uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = g < n_groups;
     br_meta mt{};
-    node_rec *r = nullptr;
     if (active) {
-        mt = meta[g]; // meta/scratch by thread slot; record by group index
-        r = &out[perm ? perm[g] : g];
-        if (mt.br_len == 0) { // error group: dead record (err already flagged)
-            r->s = mt.s;
-            r->e = mt.e;
-            r->seg = mt.seg;
-            r->pad_ = 0;
-            r->depth = -1;
-            r->ref_len = 0;
+        mt = meta[g]; // meta/scratch by thread slot
+        if (mt.br_len == 0) // error group: no node (err already flagged)
             active = false;
-        }
     }
     if (active) {
     int d = mt.d;
@@ -1539,8 +1589,8 @@ __global__ void __launch_bounds__(BLOCK) k_branch_hash(
     const uint64_t inl_stride = scratch_stride;
 #endif
     branch_tail(mt, subtree, keys, key_stride, br_hash, inl, inl_stride,
-                lds + (uint64_t)threadIdx.x * SLOT_EXT, r, seg_roots,
-                child_refs, child_lens, hist_l, bhash_by_s, urows,
+                lds + (uint64_t)threadIdx.x * SLOT_EXT, recs, depths, n,
+                seg_roots, child_refs, child_lens, hist_l, bhash_by_s, urows,
                 urowidx ? urowidx[g] : 0xFFFFFFFFu);
     } // active
     __syncthreads();
@@ -1561,7 +1611,8 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
     const node_rec *__restrict__ L, const uint32_t *__restrict__ gs,
     uint32_t n_groups /* class-0 groups of this chunk */,
     const int8_t *__restrict__ lcp, const uint8_t *__restrict__ keys,
-    uint64_t key_stride, int d, int subtree, node_rec *__restrict__ out,
+    uint64_t key_stride, int d, int subtree, node_rec *__restrict__ recs,
+    uint8_t *__restrict__ depths, uint64_t n,
     const uint32_t *__restrict__ perm /* class-0 slice */,
     uint8_t *__restrict__ seg_roots, uint8_t *__restrict__ child_refs,
     uint8_t *__restrict__ child_lens, uint32_t *__restrict__ pending,
@@ -1596,7 +1647,8 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
             }
         br_meta mt;
         mt.s = sized_ok ? w0[0] : L[j].s;
-        mt.e = sized_ok ? w1[nmem - 1] : L[jend - 1].e;
+        // select, not w1[nmem - 1]: a run-time index puts w1 in scratch
+        mt.e = sized_ok ? (nmem == 3 ? w1[2] : w1[1]) : L[jend - 1].e;
         mt.seg = sized_ok ? w2[0] : L[j].seg;
         mt.d = (uint8_t)d;
         int8_t pl = lcp[mt.s], pr = lcp[mt.e];
@@ -1620,15 +1672,8 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
                 }
         }
         mt.flags = stored ? 1 : 0;
-        node_rec *r = &out[gg];
-        if (!order_ok || payload > 116) {
+        if (!order_ok || payload > 116) { // error group: no node
             atomicOr(err, 1u << E_INTERNAL);
-            r->s = mt.s;
-            r->e = mt.e;
-            r->seg = mt.seg;
-            r->pad_ = 0;
-            r->depth = -1;
-            r->ref_len = 0;
         } else {
             int h = rlp_list_hdr_len(payload);
             mt.br_len = (uint16_t)(h + payload);
@@ -1687,7 +1732,8 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
             // ext scratch aliases the message slot: branch_tail reads the
             // inline words before any wrap reuses it
             branch_tail(mt, subtree, keys, key_stride, br_hash, slot64, 1,
-                        slot, r, seg_roots, child_refs, child_lens, hist_l,
+                        slot, recs, depths, n, seg_roots, child_refs,
+                        child_lens, hist_l,
                         nullptr, nullptr, 0xFFFFFFFFu);
         }
     }
@@ -3282,6 +3328,24 @@ extern "C" int sre_keccak_batch_device(sre_ctx *ctx, const void *d_in, uint64_t 
     return 0;
 }
 
+// Messages of any length (sre_keccak_batch_device is one block, <= 135 B).
+extern "C" int sre_keccak_long_device(sre_ctx *ctx, const void *d_in, uint64_t stride,
+                                      uint32_t len, uint64_t n, void *d_out)
+{
+    HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (len > stride) {
+        set_err(ctx, "sre_keccak_long_device: len > stride");
+        return -1;
+    }
+    if (n == 0)
+        return 0;
+    uint64_t blocks = (n + BLOCK - 1) / BLOCK;
+    LAUNCH(ctx, k_keccak_long, (uint32_t)blocks, BLOCK, ctx->stream,
+           (const uint8_t *)d_in, stride, len, n, (uint8_t *)d_out);
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
 // Pool-backed transient device buffer (stream-ordered reuse is safe: all
 // work runs on ctx->stream).
 struct DBuf {
@@ -3489,9 +3553,9 @@ struct level_carry {
 // usually gets its predecessor's buffer back). lcnt/loff (the per-wave
 // select counts and their scan) are sized once per pass.
 struct level_bufs {
-    DBuf Lbuf, lcnt, loff, newn, gs, scratch, meta, urows, urow_cnt, urowidx;
+    DBuf Lbuf, lcnt, loff, gs, scratch, meta, urows, urow_cnt, urowidx;
     explicit level_bufs(sre_ctx *c)
-        : Lbuf(c), lcnt(c), loff(c), newn(c), gs(c), scratch(c), meta(c),
+        : Lbuf(c), lcnt(c), loff(c), gs(c), scratch(c), meta(c),
           urows(c), urow_cnt(c), urowidx(c)
     {
     }
@@ -3542,7 +3606,6 @@ static int select_level(sre_ctx *ctx, const level_in &in, level_bufs &bufs,
         HIP_CHECK(ctx, bufs.Lbuf.alloc(w.n_level * sizeof(node_rec)));
     w.L = bufs.Lbuf.as<node_rec>();
     const uint64_t BR_CHUNK = br_chunk_groups();
-    HIP_CHECK(ctx, bufs.newn.alloc((uint64_t)w.n_groups * sizeof(node_rec)));
     HIP_CHECK(ctx, bufs.gs.alloc(((uint64_t)w.n_groups + 1) * 4));
     w.chunk = w.n_groups < BR_CHUNK ? w.n_groups : BR_CHUNK;
     HIP_CHECK(ctx, bufs.scratch.alloc(w.chunk * (SRE_SCRATCH_ROWMAJOR
@@ -3631,7 +3694,6 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
     const uint64_t chunk = w.chunk;
     const bool pipe2 = w.pipe2, updates = in.updates_kind >= 0;
     uint32_t *gs = bufs.gs.as<uint32_t>();
-    node_rec *newn = bufs.newn.as<node_rec>();
     uint32_t *pend = carry.pend.as<uint32_t>();
     Event ev_asm[2] = {Event(hipEventDisableTiming), Event(hipEventDisableTiming)};
     Event ev_hash[2] = {Event(hipEventDisableTiming),
@@ -3677,12 +3739,14 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
         if (c0m)
             LAUNCH(ctx, k_branch_fused1, grid_for(c0m), BLOCK, ctx->stream, w.L,
                    gs + g0, c0m, in.lcp, in.keys, in.key_stride, d, in.subtree,
-                   newn + g0, w.perm.as<uint32_t>() + g0, in.seg_roots,
+                   in.recs, in.depths, in.n, w.perm.as<uint32_t>() + g0,
+                   in.seg_roots,
                    in.child_refs, in.child_lens, pend, in.err);
         if (c0t)
             LAUNCH(ctx, k_branch_fused1, grid_for(c0t), BLOCK, s_asm, w.L,
                    gs + g0, c0t, in.lcp, in.keys, in.key_stride, d, in.subtree,
-                   newn + g0, w.perm.as<uint32_t>() + g0 + c0m, in.seg_roots,
+                   in.recs, in.depths, in.n,
+                   w.perm.as<uint32_t>() + g0 + c0m, in.seg_roots,
                    in.child_refs, in.child_lens, pend, in.err);
         if (pipe2)
             HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ev_asm[buf].ev, 0));
@@ -3705,7 +3769,7 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
         if (gsplit)
             LAUNCH(ctx, k_branch_hash, grid_for(gsplit), BLOCK, ctx->stream, scr,
                    chunk, mt, gsplit, in.keys, in.key_stride, in.subtree,
-                   newn + g0, d_perm, in.seg_roots, in.child_refs,
+                   in.recs, in.depths, in.n, in.seg_roots, in.child_refs,
                    in.child_lens, pend, in.err, in.bhash,
                    updates ? bufs.urows.as<sre_update_row>() : nullptr,
                    updates ? bufs.urowidx.as<uint32_t>() : nullptr);
@@ -3731,17 +3795,6 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
         HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ev_asm[0].ev, 0));
     }
     HIP_CHECK(ctx, timer.stop(ctx->stream));
-    return 0;
-}
-
-// Put level d's new nodes in place for the levels that wait for them (queued
-// behind the branch chunks; the caller synchronises).
-static int place_new_nodes(sre_ctx *ctx, const level_in &in, level_bufs &bufs,
-                           uint32_t n_groups)
-{
-    if (n_groups)
-        LAUNCH(ctx, k_place_nodes, grid_for(n_groups), BLOCK, ctx->stream,
-               bufs.newn.as<node_rec>(), n_groups, in.n, in.recs, in.depths);
     return 0;
 }
 
@@ -3786,8 +3839,7 @@ static int run_levels(sre_ctx *ctx, const level_in &in, pass_out *po,
                    cap.capacity, in.err,
                    in.updates_kind >= 0 ? in.bhash : nullptr);
         if (partition_classes(ctx, in, proof.n, bufs, w) ||
-            run_branch_chunks(ctx, in, proof, carry, bufs, w, timer) ||
-            place_new_nodes(ctx, in, bufs, w.n_groups))
+            run_branch_chunks(ctx, in, proof, carry, bufs, w, timer))
             return -1;
         HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         float ms = 0;

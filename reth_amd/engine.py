@@ -384,11 +384,21 @@ class StateRootEngine:
         first so pending writes to in_tensor are visible (the engine
         synchronizes its stream before returning, so later torch ops are
         safe the other way around)."""
+        return self._keccak_device(self._lib.sre_keccak_batch_device,
+                                   in_tensor, msg_len, out_tensor)
+
+    def keccak_long_device(self, in_tensor, msg_len, out_tensor):
+        """keccak_batch_device without the one-block limit: msg_len may be
+        anything up to the row stride (multi-block messages)."""
+        return self._keccak_device(self._lib.sre_keccak_long_device,
+                                   in_tensor, msg_len, out_tensor)
+
+    def _keccak_device(self, fn, in_tensor, msg_len, out_tensor):
         import torch
         if in_tensor.is_cuda:
             torch.cuda.synchronize(in_tensor.device)
         n, stride = in_tensor.shape
-        self._check(self._lib.sre_keccak_batch_device(
+        self._check(fn(
             ctypes.c_void_p(self._ctx), ctypes.c_void_p(in_tensor.data_ptr()),
             ctypes.c_uint64(stride), ctypes.c_uint32(msg_len), ctypes.c_uint64(n),
             ctypes.c_void_p(out_tensor.data_ptr())))
