@@ -10,6 +10,7 @@
 //   1. lcp[i] between adjacent keys (segment-aware; -1 sentinels at segment
 //      boundaries = per-account storage tries, matching the per-account
 //      independence of StorageRoot::calculate_with_cursors, trie.rs:750-876).
+//      The storage leaf kernel computes these junctions itself (junction.h).
 //   2. every leaf's parent-branch depth D = max(lcp[i], lcp[i+1]); leaf RLP
 //      (hex-prefix short key from D+1 + RLP value) assembled directly in a
 //      per-lane LDS slot, hashed by a per-lane Keccak-f[1600] sponge with the
@@ -47,6 +48,7 @@
 #include <memory>
 
 #include "../../include/sre.h"
+#include "junction.h"
 
 #define BLOCK 256u
 
@@ -481,26 +483,31 @@ __global__ void k_seg_flags_lcp(const sre_storage_entry *__restrict__ st,
     lcp[i] = (int8_t)l;
 }
 
-// seg_id = inclusive_scan(flags) - 1: the host computes the exclusive scan,
-// this fixes it up per element (excl + flag - 1).
-__global__ void k_seg_fix(const uint32_t *__restrict__ flags,
-                          uint32_t *__restrict__ seg_id, uint64_t ns)
-{
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ns)
-        return;
-    seg_id[i] += flags[i] - 1;
-}
-
+// One sweep of the flags and their exclusive scan (computed by the host):
+// seg_id = inclusive_scan(flags) - 1, fixed up in place per element
+// (excl + flag - 1), and the first entry of every segment.
+// With seg_roots (storage pass, after the leaf kernel): a segment whose
+// start is also its end (lcp[i + 1] == -1) is a single-slot trie, whose
+// root is its leaf's hash: a 64-nibble leaf RLP is >= 35 B, so recs[i].ref
+// is always 0xa0 || hash there.
 __global__ void k_seg_starts(const uint32_t *__restrict__ flags,
-                             const uint32_t *__restrict__ seg_id, uint64_t ns,
-                             uint32_t *__restrict__ seg_start)
+                             uint32_t *__restrict__ seg_id, uint64_t ns,
+                             uint32_t *__restrict__ seg_start,
+                             const int8_t *__restrict__ lcp,
+                             const node_rec *__restrict__ recs,
+                             uint8_t *__restrict__ seg_roots)
 {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ns)
         return;
-    if (flags[i])
-        seg_start[seg_id[i]] = (uint32_t)i;
+    const uint32_t f = flags[i];
+    const uint32_t seg = seg_id[i] + f - 1;
+    seg_id[i] = seg;
+    if (f) {
+        seg_start[seg] = (uint32_t)i;
+        if (seg_roots && lcp[i + 1] == -1)
+            memcpy(seg_roots + 32ull * seg, recs[i].ref + 1, 32);
+    }
 }
 
 __global__ void k_seg_acct(const sre_storage_entry *__restrict__ st,
@@ -564,13 +571,46 @@ __global__ void k_lcp_account(const sre_account_entry *__restrict__ acct, uint64
 // by register byte-funnels. No LDS traffic, no per-nibble loads, and the
 // keccak pad byte rides the value funnel as a 5th input word. The slow
 // path keeps the original byte-wise LDS assembly.
+//
+// The kernel also computes the junctions (junction.h) the trie shape comes
+// from, so no separate pass reads the entries first: lane i loads its whole
+// entry and entry i+1's two keys (a second load of lines its neighbour lane
+// pulls anyway), computes the right junction and stores lcp[i+1] /
+// flags[i+1]; the left junction is lane i-1's finished result, moved across
+// with one shuffle. The first lane of a wave computes its left junction
+// itself. Lane 0 stores lcp[0] / flags[0], lane ns-1 stores lcp[ns];
+// st[-1] and st[ns] are never read. A junction travels as its lcp byte in
+// bits 0..7 and the contract violation in bit 8. A lane with a violating
+// junction on either side flags it and, like a zero-valued slot, writes
+// neither record nor depth byte (a duplicate key's 64 shared nibbles would
+// put `from` at 65); the host checks err before any level runs.
+// Records carry seg = 0: segment ids exist only after this kernel (scan of
+// the flags) and are looked up per entry where they are consumed.
 #define SLOT_STO 136
+__device__ __forceinline__ void words_of(uint4 a, uint4 b, uint64_t w[4])
+{
+    w[0] = (uint64_t)a.x | ((uint64_t)a.y << 32);
+    w[1] = (uint64_t)a.z | ((uint64_t)a.w << 32);
+    w[2] = (uint64_t)b.x | ((uint64_t)b.y << 32);
+    w[3] = (uint64_t)b.z | ((uint64_t)b.w << 32);
+}
+
+// junction of entries l, r (adjacent, both inside the array), packed
+__device__ __forceinline__ int packed_junction(const uint64_t l_acct[4],
+                                               const uint64_t l_slot[4],
+                                               const uint64_t r_acct[4],
+                                               const uint64_t r_slot[4])
+{
+    bool bad;
+    int l = storage_junction(l_acct, l_slot, r_acct, r_slot, &bad);
+    return (l & 0xFF) | (bad ? 0x100 : 0);
+}
+
 __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
     const sre_storage_entry *__restrict__ st, uint64_t ns,
-    const int8_t *__restrict__ lcp, const uint32_t *__restrict__ seg_id,
+    int8_t *__restrict__ lcp, uint32_t *__restrict__ flags,
     node_rec *__restrict__ recs, uint8_t *__restrict__ depths,
-    uint32_t *__restrict__ hist, uint8_t *__restrict__ seg_roots,
-    uint32_t *__restrict__ err)
+    uint32_t *__restrict__ hist, uint32_t *__restrict__ err)
 {
     __shared__ __align__(16) uint8_t lds[BLOCK * SLOT_STO + 66 * 4];
     uint32_t *hist_l = (uint32_t *)(lds + BLOCK * SLOT_STO);
@@ -579,28 +619,55 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
     __syncthreads();
 
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < ns) {
-        int8_t l0 = lcp[i], l1 = lcp[i + 1];
+    const bool live = i < ns;
+    uint64_t A[4], K[6], V[6];
+    int jr = 0xFF; // right junction; the array end is a boundary (-1)
+    if (live) {
+        // entries are 96 B at a 16-B-aligned base -> acct_key/slot_key/value
+        // are 16-B aligned; pull each as a dwordx4 pair once.
+        const uint4 *e4 = (const uint4 *)&st[i];
+        uint4 aa = e4[0], ac = e4[1], ka = e4[2], kc = e4[3], va = e4[4],
+              vc = e4[5];
+        words_of(aa, ac, A);
+        words_of(ka, kc, K);
+        words_of(va, vc, V);
+        if (i + 1 < ns) {
+            const uint4 *n4 = (const uint4 *)&st[i + 1];
+            uint64_t NA[4], NK[4];
+            words_of(n4[0], n4[1], NA);
+            words_of(n4[2], n4[3], NK);
+            jr = packed_junction(A, K, NA, NK);
+            lcp[i + 1] = (int8_t)jr;
+            flags[i + 1] = (jr & 0xFF) == 0xFF ? 1u : 0u;
+        } else {
+            lcp[ns] = -1;
+        }
+    }
+    // every lane of the wave is here: the shuffle runs in uniform flow
+    int jl = __shfl_up(jr, 1);
+    if (live && (threadIdx.x & 63) == 0) {
+        if (i == 0) {
+            jl = 0xFF;
+            lcp[0] = -1;
+            flags[0] = 1;
+        } else {
+            const uint4 *p4 = (const uint4 *)&st[i - 1];
+            uint64_t PA[4], PK[4];
+            words_of(p4[0], p4[1], PA);
+            words_of(p4[2], p4[3], PK);
+            jl = packed_junction(PA, PK, A, K);
+        }
+    }
+    if (live) {
+        int l0 = (int8_t)jl, l1 = (int8_t)jr;
         int D = l0 > l1 ? l0 : l1;
         int from = D + 1;
+        const bool bad = ((jl | jr) & 0x100) != 0;
 
         const uint8_t *key = st[i].slot_key;
         const uint8_t *val = st[i].value;
 
-        // entries are 96 B at a 16-B-aligned base -> slot_key/value are
-        // 16-B aligned; pull both as dwordx4 pairs once.
-        const uint4 *e4 = (const uint4 *)&st[i];
-        uint4 ka = e4[2], kc = e4[3], va = e4[4], vc = e4[5];
-        uint64_t K[6], V[6];
-        K[0] = (uint64_t)ka.x | ((uint64_t)ka.y << 32);
-        K[1] = (uint64_t)ka.z | ((uint64_t)ka.w << 32);
-        K[2] = (uint64_t)kc.x | ((uint64_t)kc.y << 32);
-        K[3] = (uint64_t)kc.z | ((uint64_t)kc.w << 32);
         K[4] = 0; K[5] = 0;
-        V[0] = (uint64_t)va.x | ((uint64_t)va.y << 32);
-        V[1] = (uint64_t)va.z | ((uint64_t)va.w << 32);
-        V[2] = (uint64_t)vc.x | ((uint64_t)vc.y << 32);
-        V[3] = (uint64_t)vc.z | ((uint64_t)vc.w << 32);
         V[4] = 0x01; // keccak pad start byte, rides the value funnel
         V[5] = 0;
 
@@ -613,8 +680,12 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
         else if (V[3]) j0 = 24 + (__builtin_ctzll(V[3]) >> 3);
         else           j0 = 32;
         int vlen = 32 - j0;
-        if (vlen == 0) {
+        if (bad)
+            atomicOr(err, 1u << E_UNSORTED_STORAGE);
+        if (vlen == 0)
             atomicOr(err, 1u << E_ZERO_VALUE);
+        if (bad || vlen == 0) {
+            // rejected entry: no record, no depth byte
         } else if (D <= 13) {
             // ---- fast register path ----
             int kb = (from + 1) >> 1; // suffix start byte, 0..7
@@ -702,7 +773,6 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
             s[16] = 0x8000000000000000ull;
             keccak_f(s);
 
-            uint32_t seg = seg_id[i];
             if (len >= 32) {
                 // compose the whole 48-B record in registers, store as
                 // 3 x dwordx4 (byte-wise ref stores were address-bound)
@@ -713,7 +783,7 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
                 uint32_t w[12];
                 w[0] = (uint32_t)i;
                 w[1] = (uint32_t)(i + 1);
-                w[2] = seg;
+                w[2] = 0;
                 w[3] = (uint32_t)(uint8_t)(int8_t)D | (33u << 8) |
                        (0xa0u << 16) | ((uint32_t)(s[0] & 0xFF) << 24);
                 w[4] = (uint32_t)(s[0] >> 8);
@@ -734,7 +804,7 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
                 node_rec *r = &recs[i];
                 r->s = (uint32_t)i;
                 r->e = (uint32_t)(i + 1);
-                r->seg = seg;
+                r->seg = 0;
                 r->depth = (int8_t)D;
                 r->ref_len = (uint8_t)len;
                 uint64_t mm[4] = {m0, m1, m2, m3};
@@ -743,11 +813,9 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
                 r->pad_ = D >= 0 ? nib_of(key, D) : 0;
             }
             depths[i] = (uint8_t)(D + 1);
+            // D == -1 (single-slot trie): the record's hash is the segment
+            // root; k_seg_starts copies it out once the segment ids exist
             atomicAdd(&hist_l[D + 1], 1u);
-            if (D == -1) { // single-slot storage trie: root = keccak(leaf RLP)
-                uint64_t *sr = (uint64_t *)(seg_roots + 32ull * seg);
-                sr[0] = s[0]; sr[1] = s[1]; sr[2] = s[2]; sr[3] = s[3];
-            }
         } else {
             // ---- slow LDS path (deep shared prefixes) ----
             uint8_t *slot = lds + (uint64_t)threadIdx.x * SLOT_STO;
@@ -776,8 +844,7 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
             node_rec *r = &recs[i];
             r->s = (uint32_t)i;
             r->e = (uint32_t)(i + 1);
-            uint32_t seg = seg_id[i];
-            r->seg = seg;
+            r->seg = 0;
             r->depth = (int8_t)D;
             uint8_t rl;
             make_ref(slot, len, hash, r->ref, &rl);
@@ -785,10 +852,8 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
             // child nibble at the parent branch (known now; saves the branch
             // assembler a scattered key gather per member)
             r->pad_ = D >= 0 ? nib_of(key, D) : 0;
-            depths[i] = (uint8_t)(D + 1);
+            depths[i] = (uint8_t)(D + 1); // D >= 14: never a segment root
             atomicAdd(&hist_l[D + 1], 1u);
-            if (D == -1)
-                memcpy(seg_roots + 32ull * seg, hash, 32);
         }
     }
     __syncthreads();
@@ -1391,7 +1456,7 @@ __device__ __forceinline__ void branch_tail(
     uint64_t inline_stride, uint8_t *ext, node_rec *recs, uint8_t *depths,
     uint64_t n, uint8_t *seg_roots, uint8_t *child_refs, uint8_t *child_lens,
     uint32_t *hist_l, uint8_t *bhash_by_s, sre_update_row *urows,
-    uint32_t urowidx_val)
+    uint32_t urowidx_val, const uint32_t *seg_by_slot)
 {
     int d = mt.d;
     int kblocks = mt.br_len / 136 + 1;
@@ -1508,17 +1573,20 @@ __device__ __forceinline__ void branch_tail(
         }
         atomicAdd(&hist_l[mt.P + 1], 1u);
     } else {
+        // storage pass: records carry no segment id; a root looks its own up
+        // by its first entry (one load per segment root, off the group path)
+        const uint32_t seg = seg_by_slot ? seg_by_slot[mt.s] : mt.seg;
         if (subtree) {
             wrap(1);
-            uint8_t *cr = child_refs + 33ull * mt.seg;
+            uint8_t *cr = child_refs + 33ull * seg;
 #pragma unroll
             for (int k = 0; k < 33; ++k)
                 if (k < wrl)
                     cr[k] = (uint8_t)(wrefw[k >> 3] >> (8 * (k & 7)));
-            child_lens[mt.seg] = wrl;
+            child_lens[seg] = wrl;
         }
         wrap(0); // standalone form: only the hash matters
-        memcpy(seg_roots + 32ull * mt.seg, whash, 32);
+        memcpy(seg_roots + 32ull * seg, whash, 32);
     }
     atomicAdd(&hist_l[65], (uint32_t)kblocks);
 }
@@ -1536,7 +1604,9 @@ __global__ void __launch_bounds__(BLOCK) k_branch_hash(
     uint8_t *__restrict__ bhash_by_s, /* updates mode: branch hash by
                                          interval start; null otherwise */
     sre_update_row *__restrict__ urows, /* updates mode: this level's rows */
-    const uint32_t *__restrict__ urowidx)
+    const uint32_t *__restrict__ urowidx,
+    const uint32_t *__restrict__ seg_by_slot /* storage pass: segment id per
+                                                entry; null = mt.seg */)
 {
     // pending[] updates are LDS-aggregated: one global atomic per counter
     // per block instead of per group (a single hot counter word saturates at
@@ -1591,7 +1661,7 @@ __global__ void __launch_bounds__(BLOCK) k_branch_hash(
     branch_tail(mt, subtree, keys, key_stride, br_hash, inl, inl_stride,
                 lds + (uint64_t)threadIdx.x * SLOT_EXT, recs, depths, n,
                 seg_roots, child_refs, child_lens, hist_l, bhash_by_s, urows,
-                urowidx ? urowidx[g] : 0xFFFFFFFFu);
+                urowidx ? urowidx[g] : 0xFFFFFFFFu, seg_by_slot);
     } // active
     __syncthreads();
     if (threadIdx.x < 66 && hist_l[threadIdx.x])
@@ -1616,7 +1686,8 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
     const uint32_t *__restrict__ perm /* class-0 slice */,
     uint8_t *__restrict__ seg_roots, uint8_t *__restrict__ child_refs,
     uint8_t *__restrict__ child_lens, uint32_t *__restrict__ pending,
-    uint32_t *__restrict__ err)
+    uint32_t *__restrict__ err,
+    const uint32_t *__restrict__ seg_by_slot /* as in k_branch_hash */)
 {
     __shared__ __align__(16) uint8_t lds[BLOCK * SLOT_F1 + 66 * 4];
     uint32_t *hist_l = (uint32_t *)(lds + BLOCK * SLOT_F1);
@@ -1734,7 +1805,7 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
             branch_tail(mt, subtree, keys, key_stride, br_hash, slot64, 1,
                         slot, recs, depths, n, seg_roots, child_refs,
                         child_lens, hist_l,
-                        nullptr, nullptr, 0xFFFFFFFFu);
+                        nullptr, nullptr, 0xFFFFFFFFu, seg_by_slot);
         }
     }
     __syncthreads();
@@ -1754,7 +1825,9 @@ __global__ void __launch_bounds__(BLOCK) k_emit_updates(
     const uint8_t *__restrict__ bhash_by_s, int kind,
     sre_update_row *__restrict__ rows, uint32_t *__restrict__ row_counter,
     const uint32_t *__restrict__ perm,
-    uint32_t *__restrict__ rowidx /* per thread slot: row slot or ~0 */)
+    uint32_t *__restrict__ rowidx /* per thread slot: row slot or ~0 */,
+    const uint32_t *__restrict__ seg_by_slot /* storage pass: segment id per
+                                                entry; null = mt.seg */)
 {
     __shared__ uint32_t lds[BLOCK];
     __shared__ uint32_t base;
@@ -1812,7 +1885,8 @@ __global__ void __launch_bounds__(BLOCK) k_emit_updates(
     // stash seg for the host-side acct_key patch; zero the rest
     for (int q = 0; q < 32; ++q)
         row->acct_key[q] = 0;
-    memcpy(row->pad_, &mt.seg, 4);
+    const uint32_t seg = seg_by_slot ? seg_by_slot[mt.s] : mt.seg;
+    memcpy(row->pad_, &seg, 4);
     row->pad_[4] = 0;
     row->removed = 0;
 }
@@ -3513,6 +3587,11 @@ struct level_in {
     const uint32_t *hist_host = nullptr; // records per depth bucket [66]
     int subtree = 0;
     uint8_t *seg_roots = nullptr, *child_refs = nullptr, *child_lens = nullptr;
+    // storage pass: segment id per entry. Its records carry seg = 0 (the ids
+    // are scanned after the leaf kernel) and the id is read as
+    // seg_by_slot[s] where it is consumed. Null in the account pass, whose
+    // records carry seg themselves.
+    const uint32_t *seg_by_slot = nullptr;
     uint32_t *err = nullptr;
     // -1 = off; 0/1 = retain TrieUpdates rows of this trie kind (bhash then
     // holds 32 B per underlying entry for branch-hash lookups)
@@ -3741,13 +3820,13 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
                    gs + g0, c0m, in.lcp, in.keys, in.key_stride, d, in.subtree,
                    in.recs, in.depths, in.n, w.perm.as<uint32_t>() + g0,
                    in.seg_roots,
-                   in.child_refs, in.child_lens, pend, in.err);
+                   in.child_refs, in.child_lens, pend, in.err, in.seg_by_slot);
         if (c0t)
             LAUNCH(ctx, k_branch_fused1, grid_for(c0t), BLOCK, s_asm, w.L,
                    gs + g0, c0t, in.lcp, in.keys, in.key_stride, d, in.subtree,
                    in.recs, in.depths, in.n,
                    w.perm.as<uint32_t>() + g0 + c0m, in.seg_roots,
-                   in.child_refs, in.child_lens, pend, in.err);
+                   in.child_refs, in.child_lens, pend, in.err, in.seg_by_slot);
         if (pipe2)
             HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ev_asm[buf].ev, 0));
         if (proof.n) // multiproof: copy path-node RLPs out of scratch
@@ -3764,7 +3843,7 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
                    gs + g0, gc, mt, in.keys, in.key_stride, in.bhash,
                    in.updates_kind, bufs.urows.as<sre_update_row>(),
                    bufs.urow_cnt.as<uint32_t>(), d_perm,
-                   bufs.urowidx.as<uint32_t>());
+                   bufs.urowidx.as<uint32_t>(), in.seg_by_slot);
         }
         if (gsplit)
             LAUNCH(ctx, k_branch_hash, grid_for(gsplit), BLOCK, ctx->stream, scr,
@@ -3772,7 +3851,8 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
                    in.recs, in.depths, in.n, in.seg_roots, in.child_refs,
                    in.child_lens, pend, in.err, in.bhash,
                    updates ? bufs.urows.as<sre_update_row>() : nullptr,
-                   updates ? bufs.urowidx.as<uint32_t>() : nullptr);
+                   updates ? bufs.urowidx.as<uint32_t>() : nullptr,
+                   in.seg_by_slot);
         if (pipe2)
             HIP_CHECK(ctx, hipEventRecord(ev_hash[buf].ev, ctx->stream));
         if (updates) {
@@ -3886,31 +3966,54 @@ struct storage_segs {
     }
 };
 
-// Input-contract violations (unsorted/orphan entries) are flagged in d_err;
-// nothing is synchronised here.
-static int segment_storage(sre_ctx *ctx, const sre_storage_entry *d_st,
-                           uint64_t ns, uint32_t *d_err, storage_segs &sg)
+// sg.flags / sg.lcp are written: scan them into seg_id, seg_start and
+// seg_acct. With `recs` (the storage pass, whose leaf kernel has run) also
+// allocates seg_roots, n_seg being known only here, and stores the roots of
+// the single-slot tries. An orphan segment is flagged in d_err; the stream
+// is left unsynchronised.
+static int segment_ids(sre_ctx *ctx, const sre_storage_entry *d_st, uint64_t ns,
+                       uint32_t *d_err, storage_segs &sg,
+                       const node_rec *recs = nullptr, DBuf *seg_roots = nullptr)
 {
-    HIP_CHECK(ctx, sg.flags.alloc(ns * 4));
-    HIP_CHECK(ctx, sg.seg_id.alloc(ns * 4));
-    HIP_CHECK(ctx, sg.lcp.alloc(ns + 1));
-    LAUNCH(ctx, k_seg_flags_lcp, grid_for(ns + 1), BLOCK, ctx->stream, d_st, ns,
-           sg.flags.as<uint32_t>(), sg.lcp.as<int8_t>(), d_err);
-    // seg_id[i] = inclusive_scan(flags)[i] - 1 (segment index of entry i)
+    // seg_id[i] = inclusive_scan(flags)[i] - 1 (segment index of entry i):
+    // the exclusive scan here, the fix-up in k_seg_starts
     if (scan_u32(ctx, sg.flags.as<uint32_t>(), sg.seg_id.as<uint32_t>(), ns,
                  &sg.n_seg))
         return -1;
-    LAUNCH(ctx, k_seg_fix, grid_for(ns), BLOCK, ctx->stream,
-           sg.flags.as<uint32_t>(), sg.seg_id.as<uint32_t>(), ns);
     HIP_CHECK(ctx, sg.seg_start.alloc((uint64_t)sg.n_seg * 4));
     HIP_CHECK(ctx, sg.seg_acct.alloc((uint64_t)sg.n_seg * 4));
+    if (seg_roots)
+        HIP_CHECK(ctx, seg_roots->alloc((uint64_t)sg.n_seg * 32));
     LAUNCH(ctx, k_seg_starts, grid_for(ns), BLOCK, ctx->stream,
            sg.flags.as<uint32_t>(), sg.seg_id.as<uint32_t>(), ns,
-           sg.seg_start.as<uint32_t>());
+           sg.seg_start.as<uint32_t>(), sg.lcp.as<int8_t>(), recs,
+           seg_roots ? seg_roots->as<uint8_t>() : nullptr);
     LAUNCH(ctx, k_seg_acct, grid_for(sg.n_seg), BLOCK, ctx->stream, d_st,
            sg.seg_start.as<uint32_t>(), sg.n_seg, ctx->d_acct, ctx->na,
            sg.seg_acct.as<uint32_t>(), d_err);
     return 0;
+}
+
+static int alloc_segs(sre_ctx *ctx, uint64_t ns, storage_segs &sg)
+{
+    HIP_CHECK(ctx, sg.flags.alloc(ns * 4));
+    HIP_CHECK(ctx, sg.seg_id.alloc(ns * 4));
+    HIP_CHECK(ctx, sg.lcp.alloc(ns + 1));
+    return 0;
+}
+
+// Segmentation on its own, for a caller that hashes no leaf
+// (sre_root_from_nodes picks the tries to rebuild from it). Input-contract
+// violations (unsorted/orphan entries) are flagged in d_err; nothing is
+// synchronised here.
+static int segment_storage(sre_ctx *ctx, const sre_storage_entry *d_st,
+                           uint64_t ns, uint32_t *d_err, storage_segs &sg)
+{
+    if (alloc_segs(ctx, ns, sg))
+        return -1;
+    LAUNCH(ctx, k_seg_flags_lcp, grid_for(ns + 1), BLOCK, ctx->stream, d_st, ns,
+           sg.flags.as<uint32_t>(), sg.lcp.as<int8_t>(), d_err);
+    return segment_ids(ctx, d_st, ns, d_err, sg);
 }
 
 // Explicit storage entries for run_storage_pass's subset mode (incremental):
@@ -3940,31 +4043,30 @@ static int run_storage_pass(sre_ctx *ctx, uint8_t *d_acct_roots, pass_out *po,
     HIP_CHECK(ctx, hist.alloc(66 * 4));
     HIP_CHECK(ctx, hipMemsetAsync(hist.p, 0, 66 * 4, ctx->stream));
     storage_segs sg(ctx);
-    if (segment_storage(ctx, d_st, ns, d_err, sg))
-        return -1;
-    const uint32_t n_seg = sg.n_seg;
-    HIP_CHECK(ctx, seg_roots.alloc((uint64_t)n_seg * 32));
-    // input-contract violations (unsorted/orphan entries) are flagged by the
-    // kernels above; bail BEFORE the trie machinery runs on garbage lcps.
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (check_err(ctx, d_err))
+    if (alloc_segs(ctx, ns, sg))
         return -1;
 
+    // the leaf kernel computes lcp and the segment flags itself; the ids
+    // are scanned from the flags while nothing waits for them
     EvTimer leaf;
     HIP_CHECK(ctx, leaf.start(ctx->stream));
     LAUNCH(ctx, k_leaf_storage, grid_for(ns), BLOCK, ctx->stream, d_st, ns,
-           sg.lcp.as<int8_t>(), sg.seg_id.as<uint32_t>(), recs.as<node_rec>(),
-           depths.as<uint8_t>(), hist.as<uint32_t>(), seg_roots.as<uint8_t>(),
-           d_err);
+           sg.lcp.as<int8_t>(), sg.flags.as<uint32_t>(), recs.as<node_rec>(),
+           depths.as<uint8_t>(), hist.as<uint32_t>(), d_err);
     HIP_CHECK(ctx, leaf.stop(ctx->stream));
+    if (segment_ids(ctx, d_st, ns, d_err, sg, recs.as<node_rec>(), &seg_roots))
+        return -1;
+    const uint32_t n_seg = sg.n_seg;
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0;
     HIP_CHECK(ctx, leaf.ms(&ms));
     po->leaf_ms += ms;
     po->leaf_count += ns;
     po->leaf_blocks += ns;
-    // a rejected entry (zero-valued slot) wrote neither record nor depth
-    // byte: stop before any level selects over unwritten slots
+    // input-contract violations (unsorted/duplicate/orphan/zero-valued
+    // entries) are flagged by the kernels above, and a rejected entry wrote
+    // neither record nor depth byte: stop before any level selects over
+    // unwritten slots
     if (check_err(ctx, d_err))
         return -1;
 
@@ -3984,6 +4086,7 @@ static int run_storage_pass(sre_ctx *ctx, uint8_t *d_acct_roots, pass_out *po,
     in.key_stride = sizeof(sre_storage_entry);
     in.hist_host = hist_host;
     in.seg_roots = seg_roots.as<uint8_t>();
+    in.seg_by_slot = sg.seg_id.as<uint32_t>();
     in.err = d_err;
     in.updates_kind = ctx->retain_updates ? 1 : -1;
     in.bhash = bhash.as<uint8_t>();
