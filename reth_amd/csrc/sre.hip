@@ -1091,16 +1091,19 @@ __global__ void __launch_bounds__(BLOCK) k_level_count(
     }
 }
 
-// Gather level d's members into the dense L (slot order) and write the
-// group starts gs[]. offs = exclusive scan of k_level_count's rows, so the
-// second row's entries are offset by n_level. The span is walked in 16
-// rounds of 64 consecutive slots (lane = slot, so the record copies stay
-// coalesced); round r's member bits sit in lanes 4r..4r+3 of the masks.
+// List level d's members: idx[p] = slot of member p (slot order), and the
+// group starts gs[] as positions in that list. The records stay where they
+// are; the branch kernels read member p as recs[idx[p]] (and its interval
+// start as idx[p] itself: every record sits at its own s). offs = exclusive
+// scan of k_level_count's rows, so the second row's entries are offset by
+// n_level. The span is walked in 16 rounds of 64 consecutive slots (lane =
+// slot, so a round's index stores are one contiguous run); round r's member
+// bits sit in lanes 4r..4r+3 of the masks.
 __global__ void __launch_bounds__(BLOCK) k_level_gather(
     const uint8_t *__restrict__ depths, const int8_t *__restrict__ lcp,
-    const node_rec *__restrict__ recs, uint64_t n, int d, uint32_t nw,
+    uint64_t n, int d, uint32_t nw,
     const uint32_t *__restrict__ offs, uint32_t n_level, uint32_t n_groups,
-    node_rec *__restrict__ L, uint32_t *__restrict__ gs)
+    uint32_t *__restrict__ idx, uint32_t *__restrict__ gs)
 {
     uint64_t w = ((uint64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
     int lane = threadIdx.x & 63;
@@ -1123,7 +1126,7 @@ __global__ void __launch_bounds__(BLOCK) k_level_gather(
         if (hit) {
             uint32_t p = pos + (uint32_t)__popcll(mh & below);
             if (p < n_level) { // always, when counts and host agree
-                copy_rec(&L[p], &recs[base + (uint64_t)r * 64 + lane]);
+                idx[p] = (uint32_t)(base + (uint64_t)r * 64 + lane);
                 if (start) {
                     uint32_t gp = gpos + (uint32_t)__popcll(ms & below);
                     if (gp < n_groups)
@@ -1330,8 +1333,12 @@ __global__ void k_class_scatter(const uint32_t *__restrict__ gs,
         inv[g] = slot;
 }
 
-__global__ void __launch_bounds__(BLOCK_A) k_branch_assemble(
-    const node_rec *__restrict__ L, const uint32_t *__restrict__ gs,
+#ifndef ASM_MEMBERS
+#define ASM_MEMBERS 4 // members whose loads one step of k_branch_assemble issues
+#endif
+__global__ void __launch_bounds__(BLOCK_A, 8) k_branch_assemble(
+    const node_rec *__restrict__ recs, const uint32_t *__restrict__ idx,
+    const uint32_t *__restrict__ gs,
     uint32_t n_groups, const int8_t *__restrict__ lcp,
     const uint8_t *__restrict__ keys, uint64_t key_stride, int d,
     uint8_t *__restrict__ scratch, uint64_t scratch_stride,
@@ -1344,9 +1351,9 @@ __global__ void __launch_bounds__(BLOCK_A) k_branch_assemble(
     uint32_t gg = perm ? perm[g] : g; // meta/scratch by thread slot g
     uint64_t j = gs[gg], jend = gs[gg + 1];
     br_meta mt;
-    mt.s = L[j].s;
-    mt.e = L[jend - 1].e;
-    mt.seg = L[j].seg;
+    mt.s = idx[j]; // a record's slot is its s
+    mt.e = recs[idx[jend - 1]].e;
+    mt.seg = recs[mt.s].seg;
     mt.d = (uint8_t)d;
     int8_t pl = lcp[mt.s], pr = lcp[mt.e];
     mt.P = pl > pr ? pl : pr;
@@ -1355,20 +1362,38 @@ __global__ void __launch_bounds__(BLOCK_A) k_branch_assemble(
     // ONE pass over the members: cache each member's child nibble (4 bits
     // into a u64), validate strictly-ascending nibbles (implies distinct,
     // in-order, and <= 16 of them), accumulate the payload.
+    // Members are taken ASM_MEMBERS at a time: their slots (contiguous in
+    // idx), then their records, each set of loads issued together, so a
+    // step costs two round trips, not two per member. The spare places of
+    // a short last step re-read the group's last member.
     uint64_t nibs = 0;
     int payload = 1 + (16 - nmem);
     bool order_ok = nmem >= 2 && nmem <= 16;
     bool stored = false; // this branch gets a TrieUpdates row (hash_mask != 0)
     {
         int prev = -1;
-        for (uint64_t mm = j; mm < jend && order_ok; ++mm) {
-            uint8_t pb = L[mm].pad_;
-            int nbm = pb & 0xF; // child nibble, stored at node creation
-            order_ok &= nbm > prev;
-            prev = nbm;
-            nibs |= (uint64_t)nbm << (4 * (mm - j));
-            payload += L[mm].ref_len;
-            stored |= (pb & 0x20) != 0; // member is a hashed branch
+        for (int c0 = 0; c0 < nmem && order_ok; c0 += ASM_MEMBERS) {
+            uint32_t sl[ASM_MEMBERS], w3[ASM_MEMBERS], w11[ASM_MEMBERS];
+#pragma unroll
+            for (int k = 0; k < ASM_MEMBERS; ++k)
+                sl[k] = idx[j + (c0 + k < nmem ? c0 + k : nmem - 1)];
+#pragma unroll
+            for (int k = 0; k < ASM_MEMBERS; ++k) {
+                const uint32_t *r32 = (const uint32_t *)&recs[sl[k]];
+                w3[k] = r32[3];   // depth, ref_len, ref[0..1]
+                w11[k] = r32[11]; // ..., pad_
+            }
+#pragma unroll
+            for (int k = 0; k < ASM_MEMBERS; ++k)
+                if (c0 + k < nmem) {
+                    uint8_t pb = (uint8_t)(w11[k] >> 24);
+                    int nbm = pb & 0xF; // child nibble, stored at node creation
+                    order_ok &= nbm > prev;
+                    prev = nbm;
+                    nibs |= (uint64_t)nbm << (4 * (c0 + k));
+                    payload += (w3[k] >> 8) & 0xFF; // ref_len
+                    stored |= (pb & 0x20) != 0; // member is a hashed branch
+                }
         }
     }
     mt.flags = stored ? 1 : 0;
@@ -1386,6 +1411,10 @@ __global__ void __launch_bounds__(BLOCK_A) k_branch_assemble(
     // digest, so block count stays per-lane (waves are still class-uniform
     // in the typical all-hashed-refs case).
     int nb = br_len / 136 + 1;
+    // everything in the meta is known: store it now, so that its registers
+    // are free while the member records are in flight (64 VGPRs, 8 waves)
+    mt.br_len = (uint16_t)br_len;
+    meta[g] = mt;
 
     byte_appender ap;
     ap.init((uint64_t *)scratch, scratch_stride, g);
@@ -1400,50 +1429,83 @@ __global__ void __launch_bounds__(BLOCK_A) k_branch_assemble(
         ap.put((uint8_t)payload);
     }
     {
-        uint64_t m = j;
-        for (int b = 0; b < 16; ++b) {
-            if (m < jend && (int)((nibs >> (4 * (m - j))) & 0xf) == b) {
-                int rl = L[m].ref_len;
-                const uint32_t *rec32 = (const uint32_t *)&L[m];
-                uint32_t w[9];
+        // member by member (ascending nibbles), empty items in the gaps;
+        // the same ASM_MEMBERS-wide steps as the validation pass
+        int prevnib = -1;
+        for (int c0 = 0; c0 < nmem; c0 += ASM_MEMBERS) {
+            uint32_t sl[ASM_MEMBERS], w[ASM_MEMBERS][9];
 #pragma unroll
-                for (int k = 0; k < 9; ++k)
-                    w[k] = rec32[3 + k]; // bytes 12..48 of the record
-                // ref byte i lives at record byte 14+i: repack into the
-                // LE word stream R and append word-wise
-                uint64_t R[5];
-                R[0] = ((uint64_t)w[0] >> 16) | ((uint64_t)w[1] << 16) |
-                       ((uint64_t)w[2] << 48);
-                R[1] = ((uint64_t)w[2] >> 16) | ((uint64_t)w[3] << 16) |
-                       ((uint64_t)w[4] << 48);
-                R[2] = ((uint64_t)w[4] >> 16) | ((uint64_t)w[5] << 16) |
-                       ((uint64_t)w[6] << 48);
-                R[3] = ((uint64_t)w[6] >> 16) | ((uint64_t)w[7] << 16) |
-                       ((uint64_t)w[8] << 48);
-                R[4] = ((uint64_t)w[8] >> 16) & 0xFF;
-                ap.put_bytes33(R, rl);
-                m++;
-            } else {
-                ap.put(0x80);
+            for (int k = 0; k < ASM_MEMBERS; ++k)
+                sl[k] = idx[j + (c0 + k < nmem ? c0 + k : nmem - 1)];
+#pragma unroll
+            for (int k = 0; k < ASM_MEMBERS; ++k) {
+                const uint32_t *rec32 = (const uint32_t *)&recs[sl[k]];
+#pragma unroll
+                for (int q = 0; q < 9; ++q)
+                    w[k][q] = rec32[3 + q]; // bytes 12..48 of the record
             }
+#pragma unroll
+            for (int k = 0; k < ASM_MEMBERS; ++k)
+                if (c0 + k < nmem) {
+                    int nbm = (int)((nibs >> (4 * (c0 + k))) & 0xF);
+                    for (int b = prevnib + 1; b < nbm; ++b)
+                        ap.put(0x80);
+                    prevnib = nbm;
+                    int rl = (w[k][0] >> 8) & 0xFF; // ref_len
+                    // ref byte i lives at record byte 14+i: repack into the
+                    // LE word stream R and append word-wise
+                    const uint32_t *v = w[k];
+                    uint64_t R[5];
+                    R[0] = ((uint64_t)v[0] >> 16) | ((uint64_t)v[1] << 16) |
+                           ((uint64_t)v[2] << 48);
+                    R[1] = ((uint64_t)v[2] >> 16) | ((uint64_t)v[3] << 16) |
+                           ((uint64_t)v[4] << 48);
+                    R[2] = ((uint64_t)v[4] >> 16) | ((uint64_t)v[5] << 16) |
+                           ((uint64_t)v[6] << 48);
+                    R[3] = ((uint64_t)v[6] >> 16) | ((uint64_t)v[7] << 16) |
+                           ((uint64_t)v[8] << 48);
+                    R[4] = ((uint64_t)v[8] >> 16) & 0xFF;
+                    ap.put_bytes33(R, rl);
+                }
         }
+        for (int b = prevnib + 1; b < 16; ++b)
+            ap.put(0x80);
         ap.put(0x80); // empty value item
     }
     ap.finish(nb); // keccak pad
-    mt.br_len = (uint16_t)br_len;
-    meta[g] = mt;
 }
 
 // Everything after a branch's RLP keccak: ref composition, extension/root
 // wraps, record/bhash/seg-root emission and the pending-histogram bumps.
 // Shared by the split hash kernel and the fused 1-block kernel.
 // A non-root node is placed where the next levels look for it: recs[mt.s]
-// (its first child's slot, consumed by now: this level reads the dense copy
-// L, never recs, and every group has its own s) with depth byte P + 1.
-// Roots and error groups store no record. The other consumed slots keep a
-// stale depth byte; that is harmless: a placed record's byte is <= d and
-// levels only descend, so a stale byte (d+1 or more) is never selected
-// again.
+// (its first child's slot) with depth byte P + 1. Roots and error groups
+// store no record. The other consumed slots keep a stale depth byte; that
+// is harmless: a placed record's byte is <= d and levels only descend, so a
+// stale byte (d+1 or more) is never selected again.
+//
+// The level's members are read from recs too (recs[idx[p]]), while this
+// store overwrites one of them. Why no reader sees a record of this level:
+// - the groups of a level have disjoint member sets (a member belongs to
+//   the one branch its depth byte and position name), and the only slot a
+//   group writes is its own first member's. So a group's members are
+//   written by that group alone, and only after it has read them:
+//   - a fused lane loads every member (validation words, then the emit
+//     re-read) before its own branch_tail;
+//   - in the split path a chunk's k_branch_assemble, k_proof_grab and
+//     k_emit_updates are ordered before that chunk's k_branch_hash (same
+//     stream, or the assemble event the hash waits for);
+// - chunk k+1's assemble and the stream2 slice of the fused kernel overlap
+//   chunk k's hash, but they touch other groups' slots. Records of
+//   different groups may share a 128-B line; the stores are whole-record
+//   dwordx4 stores and never touch a neighbour's bytes;
+// - k_proof_grab's search reads idx (written by the select, not here) and
+//   the e of a group's LAST member, which no group of this level writes;
+// - k_capture_L runs before any branch kernel of its level, after the
+//   previous level's streams have joined;
+// - depths[] is written here and read only by the next level's select.
+// This holds in every mode (root, subtree, updates, proof, retaining /
+// incremental): they differ in which of these kernels run, not in order.
 // `inline_src64` points at the branch RLP's word 0 for the <32-B inline
 // case, with `inline_stride` u64s between message words (column-major
 // scratch: stride = chunk; LDS row: stride = 1). `ext` is a per-lane LDS
@@ -1678,7 +1740,7 @@ __global__ void __launch_bounds__(BLOCK) k_branch_hash(
 // scratch across kernels).
 #define SLOT_F1 136
 __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
-    const node_rec *__restrict__ L, const uint32_t *__restrict__ gs,
+    const uint32_t *__restrict__ idx, const uint32_t *__restrict__ gs,
     uint32_t n_groups /* class-0 groups of this chunk */,
     const int8_t *__restrict__ lcp, const uint8_t *__restrict__ keys,
     uint64_t key_stride, int d, int subtree, node_rec *__restrict__ recs,
@@ -1705,22 +1767,29 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
         // records' cache lines, so the emit pass re-reads them from L1 —
         // caching the full 48-B records in registers measured as scratch
         // spills instead.
-        uint32_t w3[3], w11[3], w0[3], w1[3], w2[3];
+        // The members' slots come first, all at once (they are contiguous
+        // in idx): the record loads hang on them, and mt.s is member 0's
+        // slot itself, so word 0 of the records is never loaded.
+        uint32_t im[3];
+#pragma unroll
+        for (int m = 0; m < 3; ++m)
+            im[m] = idx[(sized_ok && m < nmem) ? j + m : j];
+        uint32_t w3[3], w11[3], w1[3], w2[3];
 #pragma unroll
         for (int m = 0; m < 3; ++m)
             if (sized_ok && m < nmem) {
-                const uint32_t *r32 = (const uint32_t *)&L[j + m];
-                w0[m] = r32[0];
+                const uint32_t *r32 = (const uint32_t *)&recs[im[m]];
                 w1[m] = r32[1];
                 w2[m] = r32[2];
                 w3[m] = r32[3];
                 w11[m] = r32[11];
             }
         br_meta mt;
-        mt.s = sized_ok ? w0[0] : L[j].s;
-        // select, not w1[nmem - 1]: a run-time index puts w1 in scratch
-        mt.e = sized_ok ? (nmem == 3 ? w1[2] : w1[1]) : L[jend - 1].e;
-        mt.seg = sized_ok ? w2[0] : L[j].seg;
+        mt.s = im[0];
+        // select, not w1[nmem - 1]: a run-time index puts w1 in scratch.
+        // An ill-sized group is an error group: its e/seg are never used.
+        mt.e = sized_ok ? (nmem == 3 ? w1[2] : w1[1]) : mt.s;
+        mt.seg = sized_ok ? w2[0] : 0;
         mt.d = (uint8_t)d;
         int8_t pl = lcp[mt.s], pr = lcp[mt.e];
         mt.P = pl > pr ? pl : pr;
@@ -1769,7 +1838,7 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
                         prevnib = nbm;
                         int rl = (w3[m] >> 8) & 0xFF;
                         const uint32_t *rec32 =
-                            (const uint32_t *)&L[j + m]; // L1-hot re-read
+                            (const uint32_t *)&recs[im[m]]; // L1-hot re-read
                         uint32_t v[9];
 #pragma unroll
                         for (int k = 0; k < 9; ++k)
@@ -1819,7 +1888,8 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
 // atomic bump. kind: 0 account trie, 1 storage trie (acct_key patched on
 // host from the stashed seg id).
 __global__ void __launch_bounds__(BLOCK) k_emit_updates(
-    const node_rec *__restrict__ L, const uint32_t *__restrict__ gs,
+    const node_rec *__restrict__ recs, const uint32_t *__restrict__ idx,
+    const uint32_t *__restrict__ gs,
     uint32_t n_groups, const br_meta *__restrict__ meta,
     const uint8_t *__restrict__ keys, uint64_t key_stride,
     const uint8_t *__restrict__ bhash_by_s, int kind,
@@ -1849,12 +1919,13 @@ __global__ void __launch_bounds__(BLOCK) k_emit_updates(
     uint16_t state = 0, tree = 0, hashm = 0;
     int nh = 0;
     for (uint64_t m = j; m < jend; ++m) {
-        uint8_t pb = L[m].pad_;
+        const uint32_t ms = idx[m]; // the member's slot, and its s
+        uint8_t pb = recs[ms].pad_;
         int b = pb & 0xF;
         state |= (uint16_t)(1u << b);
         if (pb & 0x20) { // child subtree top is a hashed branch
             hashm |= (uint16_t)(1u << b);
-            memcpy(row->hashes[nh++], bhash_by_s + 32ull * L[m].s, 32);
+            memcpy(row->hashes[nh++], bhash_by_s + 32ull * ms, 32);
         }
         if (pb & 0x10) // child branch is itself stored
             tree |= (uint16_t)(1u << b);
@@ -1998,7 +2069,7 @@ __global__ void k_proof_ti64(const sre_storage_entry *__restrict__ st,
 }
 
 __device__ __forceinline__ void proof_grab_one(
-    const node_rec *L, const uint32_t *gs, const br_meta *meta,
+    const br_meta *meta,
     const uint8_t *scratch, uint64_t scratch_stride, const uint32_t *inv,
     const uint8_t *keys, uint64_t key_stride, uint32_t t, uint32_t g,
     proof_row *rows, uint32_t *cnt, uint32_t cap, uint32_t *err)
@@ -2033,7 +2104,8 @@ __device__ __forceinline__ void proof_grab_one(
 }
 
 // find the chunk-local group covering leaf index pos, or ~0u
-__device__ __forceinline__ uint32_t proof_find_group(const node_rec *L,
+__device__ __forceinline__ uint32_t proof_find_group(const node_rec *recs,
+                                                     const uint32_t *idx,
                                                      const uint32_t *gs,
                                                      uint32_t n_groups,
                                                      uint32_t pos)
@@ -2041,7 +2113,7 @@ __device__ __forceinline__ uint32_t proof_find_group(const node_rec *L,
     uint32_t lo = 0, hi = n_groups;
     while (lo < hi) {
         uint32_t mid = (lo + hi) / 2;
-        if (L[gs[mid]].s <= pos)
+        if (idx[gs[mid]] <= pos) // first member's slot = the group's s
             lo = mid + 1;
         else
             hi = mid;
@@ -2049,12 +2121,13 @@ __device__ __forceinline__ uint32_t proof_find_group(const node_rec *L,
     if (lo == 0)
         return ~0u;
     uint32_t g = lo - 1;
-    if (pos >= L[gs[g + 1] - 1].e)
+    if (pos >= recs[idx[gs[g + 1] - 1]].e)
         return ~0u;
     return g;
 }
 
-__global__ void k_proof_grab(const node_rec *__restrict__ L,
+__global__ void k_proof_grab(const node_rec *__restrict__ recs,
+                             const uint32_t *__restrict__ idx,
                              const uint32_t *__restrict__ gs, uint32_t n_groups,
                              const br_meta *__restrict__ meta,
                              const uint8_t *__restrict__ scratch,
@@ -2071,13 +2144,13 @@ __global__ void k_proof_grab(const node_rec *__restrict__ L,
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_t)
         return;
-    uint32_t g1 = proof_find_group(L, gs, n_groups, ti[t]);
-    uint32_t g2 = ti2 ? proof_find_group(L, gs, n_groups, ti2[t]) : g1;
+    uint32_t g1 = proof_find_group(recs, idx, gs, n_groups, ti[t]);
+    uint32_t g2 = ti2 ? proof_find_group(recs, idx, gs, n_groups, ti2[t]) : g1;
     if (g1 != ~0u)
-        proof_grab_one(L, gs, meta, scratch, scratch_stride, inv, keys,
+        proof_grab_one(meta, scratch, scratch_stride, inv, keys,
                        key_stride, t, g1, rows, cnt, cap, err);
     if (g2 != ~0u && g2 != g1)
-        proof_grab_one(L, gs, meta, scratch, scratch_stride, inv, keys,
+        proof_grab_one(meta, scratch, scratch_stride, inv, keys,
                        key_stride, t, g2, rows, cnt, cap, err);
 }
 
@@ -2790,8 +2863,10 @@ __device__ __forceinline__ uint32_t cell_of_key(const uint8_t *key)
 
 // append every level-input record (the active nodes consumed at this level)
 // to the capture buffer: at levels < CELL_NIBBLES these are exactly the
-// cell-top nodes.
-__global__ void k_capture_L(const node_rec *__restrict__ L, uint64_t n,
+// cell-top nodes. Runs before any branch kernel of its level, so the
+// members are still as the previous levels left them.
+__global__ void k_capture_L(const node_rec *__restrict__ recs,
+                            const uint32_t *__restrict__ idx, uint64_t n,
                             const uint8_t *__restrict__ keys,
                             uint64_t key_stride, cap_row *__restrict__ out,
                             uint32_t *__restrict__ cnt, uint64_t capacity,
@@ -2816,11 +2891,12 @@ __global__ void k_capture_L(const node_rec *__restrict__ L, uint64_t n,
         return;
     }
     cap_row r;
-    copy_rec(&r.rec, &L[j]);
-    r.cell = cell_of_key(keys + (uint64_t)L[j].s * key_stride);
+    const uint32_t s = idx[j]; // the member's slot, and its s
+    copy_rec(&r.rec, &recs[s]);
+    r.cell = cell_of_key(keys + (uint64_t)s * key_stride);
     r.pad_[0] = r.pad_[1] = r.pad_[2] = 0;
     if (bhash_by_s)
-        memcpy(r.bhash, bhash_by_s + 32ull * L[j].s, 32);
+        memcpy(r.bhash, bhash_by_s + 32ull * s, 32);
     else
         memset(r.bhash, 0, 32);
     out[slot] = r;
@@ -3645,7 +3721,7 @@ struct level_work {
     int d = 0;
     uint64_t n_level = 0;
     uint32_t n_level32 = 0; // H2D source of gs[n_groups]: outlives the copy
-    const node_rec *L = nullptr; // merged, sorted level input
+    const uint32_t *idx = nullptr; // level input: the members' slots, sorted
     uint32_t n_groups = 0;
     uint64_t chunk = 0; // branch-pipeline chunk, in groups
     bool use_cls = false, use_fused = false, pipe2 = false;
@@ -3658,7 +3734,7 @@ struct level_work {
 };
 
 // Level d's input and groups in one select over the in-place nodes: count
-// per wave span, scan, gather into the dense L + group starts gs. Also
+// per wave span, scan, list the members' slots (idx) + group starts gs. Also
 // sizes the buffers of the branch pipeline, which runs in chunks of w.chunk
 // groups so the 552-B scratch slots stay bounded. w.n_level is the host's
 // own count (leaf histogram + pending counters); the device count must
@@ -3681,9 +3757,9 @@ static int select_level(sre_ctx *ctx, const level_in &in, level_bufs &bufs,
     }
     w.n_groups = total - n_level_dev;
     w.n_level32 = n_level_dev;
-    if (bufs.Lbuf.sz < w.n_level * sizeof(node_rec))
-        HIP_CHECK(ctx, bufs.Lbuf.alloc(w.n_level * sizeof(node_rec)));
-    w.L = bufs.Lbuf.as<node_rec>();
+    if (bufs.Lbuf.sz < w.n_level * 4)
+        HIP_CHECK(ctx, bufs.Lbuf.alloc(w.n_level * 4));
+    w.idx = bufs.Lbuf.as<uint32_t>();
     const uint64_t BR_CHUNK = br_chunk_groups();
     HIP_CHECK(ctx, bufs.gs.alloc(((uint64_t)w.n_groups + 1) * 4));
     w.chunk = w.n_groups < BR_CHUNK ? w.n_groups : BR_CHUNK;
@@ -3697,8 +3773,8 @@ static int select_level(sre_ctx *ctx, const level_in &in, level_bufs &bufs,
         HIP_CHECK(ctx, bufs.urowidx.alloc(w.chunk * 4));
     }
     LAUNCH(ctx, k_level_gather, grid, BLOCK, ctx->stream, in.depths, in.lcp,
-           in.recs, in.n, w.d, nw, off, n_level_dev, w.n_groups,
-           bufs.Lbuf.as<node_rec>(), bufs.gs.as<uint32_t>());
+           in.n, w.d, nw, off, n_level_dev, w.n_groups,
+           bufs.Lbuf.as<uint32_t>(), bufs.gs.as<uint32_t>());
     HIP_CHECK(ctx, hipMemcpyAsync(bufs.gs.as<uint32_t>() + w.n_groups,
                                   &w.n_level32, 4, hipMemcpyHostToDevice,
                                   ctx->stream));
@@ -3778,7 +3854,7 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
     Event ev_hash[2] = {Event(hipEventDisableTiming),
                         Event(hipEventDisableTiming)};
     // stream2 must not outrun state main-stream work this level depends
-    // on (L, gs, perm are ready once the partition above completes)
+    // on (idx, gs, perm are ready once the partition above completes)
     HIP_CHECK(ctx, hipEventRecord(ev_hash[0].ev, ctx->stream));
     HIP_CHECK(ctx, hipEventRecord(ev_hash[1].ev, ctx->stream));
     HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, ev_hash[0].ev, 0));
@@ -3811,18 +3887,18 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
             HIP_CHECK(ctx, hipStreamWaitEvent(s_asm, ev_hash[buf].ev, 0));
         if (gsplit)
             LAUNCH(ctx, k_branch_assemble, (gsplit + BLOCK_A - 1) / BLOCK_A,
-                   BLOCK_A, s_asm, w.L, gs + g0, gsplit, in.lcp, in.keys,
+                   BLOCK_A, s_asm, in.recs, w.idx, gs + g0, gsplit, in.lcp, in.keys,
                    in.key_stride, d, scr, chunk, mt, d_perm, in.err);
         if (pipe2)
             HIP_CHECK(ctx, hipEventRecord(ev_asm[buf].ev, s_asm));
         if (c0m)
-            LAUNCH(ctx, k_branch_fused1, grid_for(c0m), BLOCK, ctx->stream, w.L,
+            LAUNCH(ctx, k_branch_fused1, grid_for(c0m), BLOCK, ctx->stream, w.idx,
                    gs + g0, c0m, in.lcp, in.keys, in.key_stride, d, in.subtree,
                    in.recs, in.depths, in.n, w.perm.as<uint32_t>() + g0,
                    in.seg_roots,
                    in.child_refs, in.child_lens, pend, in.err, in.seg_by_slot);
         if (c0t)
-            LAUNCH(ctx, k_branch_fused1, grid_for(c0t), BLOCK, s_asm, w.L,
+            LAUNCH(ctx, k_branch_fused1, grid_for(c0t), BLOCK, s_asm, w.idx,
                    gs + g0, c0t, in.lcp, in.keys, in.key_stride, d, in.subtree,
                    in.recs, in.depths, in.n,
                    w.perm.as<uint32_t>() + g0 + c0m, in.seg_roots,
@@ -3831,7 +3907,7 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
             HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ev_asm[buf].ev, 0));
         if (proof.n) // multiproof: copy path-node RLPs out of scratch
             LAUNCH(ctx, k_proof_grab, (proof.n + BLOCK - 1) / BLOCK, BLOCK,
-                   ctx->stream, w.L, gs + g0, gc, mt, scr, chunk,
+                   ctx->stream, in.recs, w.idx, gs + g0, gc, mt, scr, chunk,
                    w.use_cls ? w.cinv.as<uint32_t>() + g0 : nullptr, in.keys,
                    in.key_stride, proof.pti, proof.pti2, proof.n, proof.rows,
                    proof.row_count, proof.row_cap, in.err);
@@ -3839,8 +3915,8 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
             // emit BEFORE hashing: children's bhash entries must not yet
             // be overwritten by this level's nodes (shared leftmost s)
             HIP_CHECK(ctx, hipMemsetAsync(bufs.urow_cnt.p, 0, 4, ctx->stream));
-            LAUNCH(ctx, k_emit_updates, grid_for(gc), BLOCK, ctx->stream, w.L,
-                   gs + g0, gc, mt, in.keys, in.key_stride, in.bhash,
+            LAUNCH(ctx, k_emit_updates, grid_for(gc), BLOCK, ctx->stream,
+                   in.recs, w.idx, gs + g0, gc, mt, in.keys, in.key_stride, in.bhash,
                    in.updates_kind, bufs.urows.as<sre_update_row>(),
                    bufs.urow_cnt.as<uint32_t>(), d_perm,
                    bufs.urowidx.as<uint32_t>(), in.seg_by_slot);
@@ -3915,7 +3991,7 @@ static int run_levels(sre_ctx *ctx, const level_in &in, pass_out *po,
             return -1;
         if (cap.depth > 0 && d == cap.depth - 1)
             LAUNCH(ctx, k_capture_L, grid_for(w.n_level), BLOCK, ctx->stream,
-                   w.L, w.n_level, in.keys, in.key_stride, cap.rows, cap.count,
+                   in.recs, w.idx, w.n_level, in.keys, in.key_stride, cap.rows, cap.count,
                    cap.capacity, in.err,
                    in.updates_kind >= 0 ? in.bhash : nullptr);
         if (partition_classes(ctx, in, proof.n, bufs, w) ||
