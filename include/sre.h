@@ -40,6 +40,35 @@
  * caller owns them afterwards. Errors: nonzero int return +
  * sre_last_error(). This library is GPU-only by design: sre_create fails
  * loudly when no HIP device is present — there is no CPU fallback.
+ *
+ * Failed calls (pinned by tests/test_gpu_rejections.py):
+ *   - A call that returns nonzero because of its INPUTS has changed nothing
+ *     the caller can observe later: the resident state is as before the
+ *     call, the cell retention and the row snapshot are as the call's entry
+ *     behaviour (below) leaves them, and sre_updates_count() is 0 after a
+ *     failed *_with_updates call. Input rejections are: unsorted or
+ *     duplicate delta rows; a storage row for an account destroyed in the
+ *     same delta; a nonzero storage row for an account that is neither
+ *     resident nor upserted by the delta; removal rows handed to
+ *     sre_root_from_nodes; the argument checks of the read-only calls and
+ *     the entry limit at upload.
+ *   - Entry behaviour: sre_apply_delta and sre_root_from_nodes disarm all
+ *     retention on entry, rejected or not. Plain sre_incremental_root
+ *     disarms the row snapshot on entry, rejected or not, and leaves cell
+ *     retention armed when it rejects. A rejected
+ *     sre_incremental_root_with_updates leaves both armed.
+ *   - A zero-valued storage row for an unknown account is a no-op deletion
+ *     and is accepted.
+ *   - The message for one kind of input error contains the same token
+ *     whichever merge path caught it: `accounts-not-sorted`,
+ *     `storage-not-sorted-or-duplicate`, `storage-for-unknown-account` (the
+ *     last covers both the destroyed and the unknown account). No input
+ *     rejection mentions `internal`.
+ *   - A call that fails AFTER it adopted a merged state (out of memory, an
+ *     internal invariant) leaves the merged state resident and ALL
+ *     retention disarmed: the next incremental call fails with
+ *     `needs sre_root_retaining first` instead of computing from records
+ *     of the previous state.
  */
 #ifndef SRE_H
 #define SRE_H
@@ -184,7 +213,9 @@ typedef struct {
  * following sre_root computes the post-delta root — the incremental-root
  * entry (DatabaseStateRoot::incremental_root semantics at the state level,
  * crates/trie/db/src/state.rs:62; BASELINE configs[4]). A storage delta row
- * for an account deleted in the same delta is invalid. */
+ * for an account deleted in the same delta is invalid, and so is a nonzero
+ * row for an account that is neither resident nor upserted by the delta;
+ * both are rejected before anything is merged ("Failed calls" above). */
 int sre_apply_delta(sre_ctx *ctx,
                     const sre_account_delta *acct_delta, uint64_t n_acct,
                     const sre_storage_entry *st_delta, uint64_t n_st);

@@ -2381,12 +2381,39 @@ __global__ void k_ovl_base_st_flags(const sre_storage_entry *__restrict__ base,
                    : 1u;
 }
 
-// delta storage row materializes iff value != 0; row for a deleted account
-// is an input error (+ order validation)
+// A nonzero delta storage row needs an owner after the merge: an upsert of
+// the same delta or a base account. (A base account the delta deletes is
+// flagged through del_keys by the callers; a zero value for an unknown
+// account is a no-op deletion.) Both account arrays are sorted — the
+// account delta's order is validated before any storage work starts.
+__device__ __forceinline__ bool
+st_row_orphan(const sre_storage_entry *__restrict__ row,
+              const sre_account_entry *__restrict__ acct, uint64_t na,
+              const sre_account_delta *__restrict__ dl_a, uint64_t n_acct)
+{
+    if (!min_be_len(row->value))
+        return false;
+    uint64_t q = lb_keys((const uint8_t *)dl_a, sizeof(sre_account_delta),
+                         n_acct, row->acct_key, 32);
+    if (q < n_acct && cmp_key32(dl_a[q].key, row->acct_key) == 0)
+        return dl_a[q].deleted != 0;
+    uint64_t p = lb_keys((const uint8_t *)acct, sizeof(sre_account_entry), na,
+                         row->acct_key, 32);
+    return !(p < na && cmp_key32(acct[p].key, row->acct_key) == 0);
+}
+
+// delta storage row materializes iff value != 0; a row for a deleted
+// account, or a nonzero row for an account that is neither resident nor
+// upserted, is an input error (+ order validation)
 __global__ void k_ovl_delta_st_flags(const sre_storage_entry *__restrict__ dl,
                                      uint64_t nd,
                                      const uint8_t *__restrict__ del_keys,
-                                     uint64_t ndel, uint32_t *__restrict__ flags,
+                                     uint64_t ndel,
+                                     const sre_account_entry *__restrict__ acct,
+                                     uint64_t na,
+                                     const sre_account_delta *__restrict__ dl_a,
+                                     uint64_t n_acct,
+                                     uint32_t *__restrict__ flags,
                                      uint32_t *__restrict__ err)
 {
     uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2399,7 +2426,8 @@ __global__ void k_ovl_delta_st_flags(const sre_storage_entry *__restrict__ dl,
     if (j > 0 && cmp_key64(dl[j - 1].acct_key, dl[j].acct_key) >= 0)
         atomicOr(err, 1u << E_UNSORTED_STORAGE);
     uint64_t q = lb_keys(del_keys, 32, ndel, dl[j].acct_key, 32);
-    if (q < ndel && cmp_key32(del_keys + 32 * q, dl[j].acct_key) == 0)
+    if ((q < ndel && cmp_key32(del_keys + 32 * q, dl[j].acct_key) == 0) ||
+        st_row_orphan(&dl[j], acct, na, dl_a, n_acct))
         atomicOr(err, 1u << E_ORPHAN_STORAGE);
     flags[j] = min_be_len(dl[j].value) ? 1u : 0u; // zero value = delete
 }
@@ -2611,10 +2639,20 @@ __global__ void k_sd_lcp_patch(const sre_account_entry *__restrict__ out,
 // flags + scans + posmap of the general storage merge; what remains is
 // the irreducible array rewrite.
 
+// k_sds_marks' per-row word, read back by the host
+enum : uint32_t {
+    SDS_MATCH = 1,  // (acct, slot) is resident: the row replaces/deletes it
+    SDS_ORPHAN = 2, // nonzero row whose account is neither resident nor upserted
+};
+
 __global__ void k_sds_marks(const sre_storage_entry *__restrict__ base,
                             uint64_t ns,
                             const sre_storage_entry *__restrict__ dl,
-                            uint64_t nst, uint32_t *__restrict__ bpos,
+                            uint64_t nst,
+                            const sre_account_entry *__restrict__ acct,
+                            uint64_t na,
+                            const sre_account_delta *__restrict__ dl_a,
+                            uint64_t n_acct, uint32_t *__restrict__ bpos,
                             uint32_t *__restrict__ match)
 {
     uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2623,10 +2661,15 @@ __global__ void k_sds_marks(const sre_storage_entry *__restrict__ base,
     uint64_t p = lb_keys((const uint8_t *)base, sizeof(sre_storage_entry), ns,
                          (const uint8_t *)&dl[k], 64);
     bpos[k] = (uint32_t)p;
-    match[k] = (p < ns && cmp_key64((const uint8_t *)&base[p],
-                                    (const uint8_t *)&dl[k]) == 0)
-                   ? 1u
-                   : 0u;
+    uint32_t m = (p < ns && cmp_key64((const uint8_t *)&base[p],
+                                      (const uint8_t *)&dl[k]) == 0)
+                     ? SDS_MATCH
+                     : 0u;
+    // the host reads match[] back anyway: the owner check rides along
+    // instead of costing a kernel and a copy of its own
+    if (st_row_orphan(&dl[k], acct, na, dl_a, n_acct))
+        m |= SDS_ORPHAN;
+    match[k] = m;
 }
 
 // wipe range of each destroyed account: [first row with this acct_key,
@@ -4302,26 +4345,31 @@ static int run_account_pass(sre_ctx *ctx, const uint8_t *d_storage_roots, int su
     return 0;
 }
 
+// The one vocabulary of validation failures (sre.h "Failed calls"): device
+// flags and host-side checks both report through here, so one kind of bad
+// input reads the same whichever merge path caught it.
+static int fail_flags(sre_ctx *ctx, uint32_t e)
+{
+    std::string msg = "input/engine error:";
+    if (e & (1u << E_UNSORTED_ACCT))
+        msg += " accounts-not-sorted";
+    if (e & (1u << E_UNSORTED_STORAGE))
+        msg += " storage-not-sorted-or-duplicate";
+    if (e & (1u << E_ORPHAN_STORAGE))
+        msg += " storage-for-unknown-account";
+    if (e & (1u << E_ZERO_VALUE))
+        msg += " zero-storage-value";
+    if (e & (1u << E_INTERNAL))
+        msg += " internal-group-invariant";
+    set_err(ctx, msg);
+    return -1;
+}
+
 static int check_err(sre_ctx *ctx, uint32_t *d_err)
 {
     uint32_t e = 0;
     HIP_CHECK(ctx, hipMemcpy(&e, d_err, 4, hipMemcpyDeviceToHost));
-    if (e) {
-        std::string msg = "input/engine error:";
-        if (e & (1u << E_UNSORTED_ACCT))
-            msg += " accounts-not-sorted";
-        if (e & (1u << E_UNSORTED_STORAGE))
-            msg += " storage-not-sorted-or-duplicate";
-        if (e & (1u << E_ORPHAN_STORAGE))
-            msg += " storage-for-unknown-account";
-        if (e & (1u << E_ZERO_VALUE))
-            msg += " zero-storage-value";
-        if (e & (1u << E_INTERNAL))
-            msg += " internal-group-invariant";
-        set_err(ctx, msg);
-        return -1;
-    }
-    return 0;
+    return e ? fail_flags(ctx, e) : 0;
 }
 
 static const uint8_t EMPTY_ROOT_H[32] = {
@@ -5399,8 +5447,9 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
                (uint64_t)Ndel <= 4096) {
         // closed-form small-delta storage merge: delta ranks + wipe-range
         // prefix sums instead of O(ns) flags/scans/posmap. Host-side
-        // validation of what k_ovl_delta_st_flags checked on device.
-        bool ok = true;
+        // validation of what k_ovl_delta_st_flags checked on device (the
+        // owner lookup against the resident accounts rides in k_sds_marks).
+        uint32_t bad = 0;
         std::vector<std::array<uint8_t, 32>> dead;
         for (uint64_t i = 0; i < n_acct; ++i)
             if (acct_delta[i].deleted) {
@@ -5408,9 +5457,9 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
                 memcpy(k.data(), acct_delta[i].key, 32);
                 dead.push_back(k);
             }
-        for (uint64_t i = 0; i < n_st && ok; ++i) {
+        for (uint64_t i = 0; i < n_st; ++i) {
             if (i && memcmp(&st_delta[i - 1], &st_delta[i], 64) >= 0)
-                ok = false; // unsorted or duplicate (acct,slot)
+                bad |= 1u << E_UNSORTED_STORAGE; // or duplicate (acct,slot)
             auto it = std::lower_bound(
                 dead.begin(), dead.end(), st_delta[i].acct_key,
                 [](const std::array<uint8_t, 32> &a, const uint8_t *b) {
@@ -5418,13 +5467,11 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
                 });
             if (it != dead.end() &&
                 memcmp(it->data(), st_delta[i].acct_key, 32) == 0)
-                ok = false; // storage row for a destroyed account
+                bad |= 1u << E_ORPHAN_STORAGE; // row for a destroyed account
         }
-        if (!ok) {
+        if (bad) {
             pool_put(ctx, acct_bytes, new_acct);
-            set_err(ctx, "apply_delta: storage delta unsorted/duplicate or "
-                         "row for a destroyed account");
-            return -1;
+            return fail_flags(ctx, bad);
         }
         DBuf bpos(ctx), match(ctx), mex(ctx), eex(ctx), dwlo(ctx), dwhi(ctx),
             dwsum(ctx);
@@ -5433,6 +5480,7 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
         if (n_st)
             LAUNCH(ctx, k_sds_marks, grid_for(n_st), BLOCK, ctx->stream,
                    ctx->d_st, ns, dl_s.as<sre_storage_entry>(), n_st,
+                   ctx->d_acct, nb, dl_a.as<sre_account_delta>(), n_acct,
                    bpos.as<uint32_t>(), match.as<uint32_t>());
         HIP_CHECK(ctx, dwlo.alloc((Ndel ? Ndel : 1) * 4));
         HIP_CHECK(ctx, dwhi.alloc((Ndel ? Ndel : 1) * 4));
@@ -5449,6 +5497,11 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
             HIP_CHECK(ctx, hipMemcpy(match_h.data(), match.p, 4 * n_st,
                                      hipMemcpyDeviceToHost));
         }
+        for (uint64_t k = 0; k < n_st; ++k)
+            if (match_h[k] & SDS_ORPHAN) { // nothing adopted or allocated yet
+                pool_put(ctx, acct_bytes, new_acct);
+                return fail_flags(ctx, 1u << E_ORPHAN_STORAGE);
+            }
         if (Ndel) {
             HIP_CHECK(ctx, hipMemcpy(wlo_h.data(), dwlo.p, 4ull * Ndel,
                                      hipMemcpyDeviceToHost));
@@ -5464,7 +5517,7 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
             bool nz = false;
             for (int q = 0; q < 32; ++q)
                 nz |= st_delta[k].value[q] != 0;
-            mex_h[k + 1] = mex_h[k] + (match_h[k] ? 1 : 0);
+            mex_h[k + 1] = mex_h[k] + ((match_h[k] & SDS_MATCH) ? 1 : 0);
             eex_h[k + 1] = eex_h[k] + (nz ? 1 : 0);
         }
         new_ns = ns - mex_h[n_st] - wsum_h[Ndel] + eex_h[n_st];
@@ -5507,7 +5560,8 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
                sdel.as<uint8_t>(), (uint64_t)Ndel, sa.as<uint32_t>());
         LAUNCH(ctx, k_ovl_delta_st_flags, grid_for(n_st + 1), BLOCK, ctx->stream,
                dl_s.as<sre_storage_entry>(), n_st, sdel.as<uint8_t>(),
-               (uint64_t)Ndel, sd.as<uint32_t>(), err.as<uint32_t>());
+               (uint64_t)Ndel, ctx->d_acct, nb, dl_a.as<sre_account_delta>(),
+               n_acct, sd.as<uint32_t>(), err.as<uint32_t>());
         uint32_t Sk = 0, Tk = 0;
         DBuf esa(ctx), esd(ctx);
         HIP_CHECK(ctx, esa.alloc((ns + 1) * 4));
@@ -5583,10 +5637,8 @@ static int apply_delta_small(sre_ctx *ctx, const sre_account_delta *acct_delta,
     // the general path's k_ovl_delta_acct_flags validates this on device;
     // closed-form ranks would silently mis-merge on unsorted input
     for (uint64_t k = 1; k < nd; ++k)
-        if (memcmp(acct_delta[k - 1].key, acct_delta[k].key, 32) >= 0) {
-            set_err(ctx, "apply_delta: account delta unsorted or duplicate");
-            return -1;
-        }
+        if (memcmp(acct_delta[k - 1].key, acct_delta[k].key, 32) >= 0)
+            return fail_flags(ctx, 1u << E_UNSORTED_ACCT);
     DBuf dl(ctx), bpos(ctx), match(ctx), mex(ctx), eex(ctx), npos(ctx),
         err(ctx);
     HIP_CHECK(ctx, dl.alloc(nd * sizeof(sre_account_delta)));
@@ -5803,6 +5855,10 @@ static int incremental_root_impl(sre_ctx *ctx,
             return -1;
         ctx->lcp_valid = false; // recomputed below
     }
+    // the merged state is adopted: the retained rows and storage roots
+    // describe the previous arrays until the end of this function refreshes
+    // them, so a failure from here on must leave retention disarmed
+    ctx->cells_valid = false;
     ctx->inc_cnt[3] = small;
     ctx->inc_cnt[4] = st_closed_form;
     uint64_t na = ctx->na;
@@ -6080,7 +6136,12 @@ extern "C" int sre_incremental_root_with_updates(
                                    out_root, true, &bitmap);
     ctx->retain_updates = false;
     if (rc) {
-        ctx->snap_valid = false;
+        ctx->updates.clear(); // no partial emission stays readable
+        // a rejected delta adopted nothing and leaves the snapshot armed;
+        // a failure after adoption disarmed the cells, and the snapshot
+        // goes with them
+        if (!ctx->cells_valid)
+            ctx->snap_valid = false;
         return rc;
     }
 

@@ -291,17 +291,21 @@ class StateRootEngine:
             ctypes.c_void_p(self._ctx), out))
         return bytes(out), self._fetch_updates()
 
-    def account_proof(self, targets) -> list:
+    def account_proof(self, targets, cap_nodes=None, cap_lens=None) -> list:
         """Account multiproof: per target, the proof node RLPs root-first
         (Proof::multiproof account surface, include/sre.h
         sre_account_proof). Present keys get the path to their leaf;
         absent keys get the exclusion proof ending at the divergence.
-        targets: list of 32-byte hashed keys."""
+        targets: list of 32-byte hashed keys. cap_nodes / cap_lens
+        override the output capacities (bytes / entries) handed to the
+        engine; the defaults hold any proof."""
         n = len(targets)
         tarr = np.frombuffer(b"".join(targets), dtype=np.uint8).reshape(n, 32)
         tarr = np.ascontiguousarray(tarr)
-        cap_nodes = n * 130 * 560 + 4096
-        cap_lens = n * 132
+        if cap_nodes is None:
+            cap_nodes = n * 130 * 560 + 4096
+        if cap_lens is None:
+            cap_lens = n * 132
         nodes = np.zeros(cap_nodes, dtype=np.uint8)
         lens = np.zeros(cap_lens, dtype=np.uint32)
         counts = np.zeros(n, dtype=np.uint32)
@@ -318,20 +322,24 @@ class StateRootEngine:
             out.append(tl)
         return out
 
-    def storage_proof(self, acct_keys, slot_keys):
+    def storage_proof(self, acct_keys, slot_keys, cap_nodes=None,
+                      cap_lens=None):
         """Storage multiproof for (account, slot) pairs. The slot may be
         absent (exclusion proof); an absent or storage-less account
         yields (EMPTY_ROOT_HASH, []) = StorageMultiProof::empty().
         Returns (roots, proofs) — per target the account's storage root
-        and the root-first node-RLP list of its storage trie."""
+        and the root-first node-RLP list of its storage trie. cap_nodes /
+        cap_lens as in account_proof."""
         n = len(acct_keys)
         assert len(slot_keys) == n
         aarr = np.ascontiguousarray(
             np.frombuffer(b"".join(acct_keys), dtype=np.uint8).reshape(n, 32))
         sarr = np.ascontiguousarray(
             np.frombuffer(b"".join(slot_keys), dtype=np.uint8).reshape(n, 32))
-        cap_nodes = n * 130 * 560 + 4096
-        cap_lens = n * 132
+        if cap_nodes is None:
+            cap_nodes = n * 130 * 560 + 4096
+        if cap_lens is None:
+            cap_lens = n * 132
         roots = np.zeros((n, 32), dtype=np.uint8)
         nodes = np.zeros(cap_nodes, dtype=np.uint8)
         lens = np.zeros(cap_lens, dtype=np.uint32)

@@ -109,7 +109,7 @@ def test_from_nodes_rejects_removal_rows(eng):
     eng.upload(acct, st)
     bad = np.zeros(1, dtype=UPDATE_DTYPE)
     bad[0]["removed"] = 1
-    with pytest.raises(RuntimeError):
+    with pytest.raises(RuntimeError, match="removal rows"):
         eng.root_from_nodes(bad)
 
 

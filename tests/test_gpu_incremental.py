@@ -134,7 +134,7 @@ def test_overlay_rejects_slot_for_deleted_account(eng):
     s[0]["acct_key"] = np.frombuffer(k, np.uint8)
     s[0]["slot_key"] = np.frombuffer(bind.keccak256(b"x"), np.uint8)
     s[0]["value"] = np.frombuffer((1).to_bytes(32, "big"), np.uint8)
-    with pytest.raises(RuntimeError):
+    with pytest.raises(RuntimeError, match="storage-for-unknown-account"):
         eng.apply_delta(d, s)
 
 
@@ -271,7 +271,7 @@ def test_incremental_requires_retention(eng):
     acct, _ = gen.gen_state_numpy(100, 0, bind.keccak256_batch)
     eng.upload(acct, np.zeros(0, bind.STORAGE_DTYPE))
     # no root_retaining yet -> error (upload invalidates retention)
-    with pytest.raises(RuntimeError):
+    with pytest.raises(RuntimeError, match="needs sre_root_retaining first"):
         eng.incremental_root(np.zeros(0, DELTA_DTYPE))
 
 

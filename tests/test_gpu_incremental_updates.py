@@ -199,7 +199,8 @@ def test_incremental_updates_requires_arming(eng):
     acct, _ = gen.gen_state_numpy(100, 0, bind.keccak256_batch)
     eng.upload(acct, np.zeros(0, bind.STORAGE_DTYPE))
     eng.root_retaining()  # plain retention does NOT arm the row snapshot
-    with pytest.raises(RuntimeError):
+    with pytest.raises(RuntimeError,
+                       match="needs sre_root_retaining_with_updates first"):
         eng.incremental_root_with_updates(np.zeros(0, DELTA_DTYPE))
 
 

@@ -268,7 +268,7 @@ def test_smallmerge_rejects_unsorted_account_delta(eng, force_small):
         d[i]["key"] = np.frombuffer(k, np.uint8)
         d[i]["nonce"] = 1
         d[i]["code_hash"] = np.frombuffer(ke, np.uint8)
-    with pytest.raises(RuntimeError):
+    with pytest.raises(RuntimeError, match="accounts-not-sorted"):
         eng.incremental_root(d)
 
 
@@ -284,5 +284,5 @@ def test_smallmerge_rejects_bad_delta(eng):
     s[0]["acct_key"] = np.frombuffer(k, np.uint8)
     s[0]["slot_key"] = np.frombuffer(bind.keccak256(b"x"), np.uint8)
     s[0]["value"] = np.frombuffer((1).to_bytes(32, "big"), np.uint8)
-    with pytest.raises(RuntimeError):
+    with pytest.raises(RuntimeError, match="storage-for-unknown-account"):
         eng.apply_delta(d, s)
