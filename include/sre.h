@@ -34,6 +34,11 @@
  *     That is ~4.29 billion leaves per GPU — 6.6x the headline 650M-leaf
  *     config; shard across GPUs (sre_subtree_roots) beyond it. Exceeding
  *     the limit is rejected at upload with an error, never truncated.
+ *   - OR plain rows: sre_upload_plain_state / sre_set_plain_state_device
+ *     take unhashed (address, ...) and (address, slot, value) rows in any
+ *     order and produce the sorted hashed arrays above on the device. Same
+ *     capacity, no duplicate address or (address, slot), values nonzero,
+ *     every storage address present among the accounts; see below.
  *
  * Thread model: all calls on one host thread per ctx; the engine is
  * internally multi-stream. The engine COPIES input buffers at upload; the
@@ -50,8 +55,13 @@
  *     duplicate delta rows; a storage row for an account destroyed in the
  *     same delta; a nonzero storage row for an account that is neither
  *     resident nor upserted by the delta; removal rows handed to
- *     sre_root_from_nodes; the argument checks of the read-only calls and
- *     the entry limit at upload.
+ *     sre_root_from_nodes; the argument checks of the read-only calls
+ *     (a wrong n at sre_download_* among them) and the entry limit at
+ *     upload; at a plain-state upload, which validates into temporaries
+ *     and swaps last: a duplicate address, a duplicate (address, slot), a
+ *     storage row of an address without account row, a zero storage value.
+ *     A rejected plain-state upload leaves all retention armed as it was
+ *     (a successful one disarms it like any upload).
  *   - Entry behaviour: sre_apply_delta and sre_root_from_nodes disarm all
  *     retention on entry, rejected or not. Plain sre_incremental_root
  *     disarms the row snapshot on entry, rejected or not, and leaves cell
@@ -62,8 +72,9 @@
  *   - The message for one kind of input error contains the same token
  *     whichever merge path caught it: `accounts-not-sorted`,
  *     `storage-not-sorted-or-duplicate`, `storage-for-unknown-account` (the
- *     last covers both the destroyed and the unknown account). No input
- *     rejection mentions `internal`.
+ *     last covers both the destroyed and the unknown account),
+ *     `zero-storage-value`, and from plain rows `duplicate-address` and
+ *     `duplicate-storage-slot`. No input rejection mentions `internal`.
  *   - A call that fails AFTER it adopted a merged state (out of memory, an
  *     internal invariant) leaves the merged state resident and ALL
  *     retention disarmed: the next incremental call fails with
@@ -381,6 +392,84 @@ int sre_get_path_counters(sre_ctx *ctx, uint64_t out[4]);
  * right root, so the root alone cannot show that reuse happened; tests
  * compare these with a key-only model of the cell rules. */
 int sre_get_incremental_counters(sre_ctx *ctx, uint64_t out[6]);
+
+/* ---- plain-state upload: hash and sort on the device -------------------
+ *
+ * One row of reth's PlainAccountState table (address -> Account;
+ * crates/storage/db-api/src/tables/mod.rs) with bytecode_hash normalised to
+ * KECCAK_EMPTY like sre_account_entry. 96 bytes, no padding besides pad_
+ * (ignored). */
+typedef struct {
+    uint8_t  address[20];
+    uint8_t  pad_[4];
+    uint64_t nonce;
+    uint8_t  balance[32];   /* big-endian U256 */
+    uint8_t  code_hash[32]; /* KECCAK_EMPTY when no code */
+} sre_plain_account;
+
+/* One row of reth's PlainStorageState dup-sorted table (address ->
+ * StorageEntry{key, value}). value big-endian U256, nonzero. 84 bytes, all
+ * uint8_t: an array of them is only 4-byte aligned. */
+typedef struct {
+    uint8_t address[20];
+    uint8_t slot[32];
+    uint8_t value[32];      /* big-endian U256, != 0 */
+} sre_plain_storage;
+
+/* Replace the resident state by the hashed and sorted form of plain rows,
+ * given in ANY order: every address and slot is hashed with keccak256,
+ * accounts are sorted by hashed address, storage by (hashed address,
+ * hashed slot), and the result is installed as engine-owned resident state
+ * exactly as if sre_upload_accounts + sre_upload_storage had been handed
+ * the sorted hashed rows. This is the work of AccountHashingStage /
+ * StorageHashingStage (crates/stages/stages/src/stages/hashing_account.rs:201,
+ * hashing_storage.rs:133-137: hash every key, sort through the ETL
+ * collector) for a whole state, and of HashedPostState::from_bundle_state +
+ * into_sorted (crates/trie/common/src/hashed_state.rs:49-70,331) for a
+ * bundle; sre_download_* then yields the HashedAccounts / HashedStorages
+ * rows those stages write.
+ *
+ * sre_upload_plain_state takes host pointers (copied to the device, then the
+ * device form runs). sre_set_plain_state_device takes device pointers
+ * (accounts 16-byte aligned, storage 4-byte aligned); it reads them only
+ * during the call, does not modify them and keeps no reference.
+ *
+ * Rejected, with the resident state and all retention as before the call
+ * ("Failed calls" above): two account rows with one address
+ * (`duplicate-address`), two storage rows with one (address, slot)
+ * (`duplicate-storage-slot`), a storage row whose address is in no account
+ * row (`storage-for-unknown-account`), a zero storage value
+ * (`zero-storage-value`), more than 2^32 - 2 rows of either kind. "Empty"
+ * accounts stay the caller's contract, unchecked. A successful call
+ * invalidates retention like any upload. */
+int sre_upload_plain_state(sre_ctx *ctx,
+                           const sre_plain_account *accounts, uint64_t na,
+                           const sre_plain_storage *storage, uint64_t ns);
+int sre_set_plain_state_device(sre_ctx *ctx, const void *d_accounts, uint64_t na,
+                               const void *d_storage, uint64_t ns);
+
+/* Read the resident state back: the sorted hashed rows, i.e. the
+ * HashedAccounts / HashedStorages table contents (tables/mod.rs:481-507).
+ * Works on whatever is resident: uploaded, borrowed, or merged by
+ * sre_apply_delta / an incremental call. n must equal the resident count
+ * (sre_resident_counts); anything else is an argument error. */
+int sre_resident_counts(sre_ctx *ctx, uint64_t *na, uint64_t *ns);
+int sre_download_accounts(sre_ctx *ctx, sre_account_entry *out, uint64_t n);
+int sre_download_storage(sre_ctx *ctx, sre_storage_entry *out, uint64_t n);
+
+/* Read-only: what the last plain-state upload that installed a state did
+ * (all zero before any), summed over its account sort and storage sort:
+ *   out[0] Keccak-f invocations (na + 2 * ns)
+ *   out[1] radix passes executed
+ *   out[2] radix passes skipped because all keys shared the digit
+ *   out[3] rows that needed a full-key comparison (they sat in a tie run:
+ *          a maximal run of >= 2 equal adjacent 64-bit sort keys)
+ *   out[4] tie runs
+ *   out[5] storage rows whose address hash was reused (0: not built)
+ * Exists for the reason sre_get_path_counters does: the sorted output alone
+ * cannot show that the tie path or the pass skipping ran (test gate
+ * SRE_HS_KEY_BITS). */
+int sre_get_hash_sort_counters(sre_ctx *ctx, uint64_t out[6]);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,7 @@
 
 #include "../../include/sre.h"
 #include "junction.h"
+#include "radix.h"
 
 #define BLOCK 256u
 
@@ -59,6 +60,8 @@ enum {
     E_ORPHAN_STORAGE = 3,
     E_ZERO_VALUE = 4,
     E_INTERNAL = 5,
+    E_DUP_ADDRESS = 6,
+    E_DUP_STORAGE = 7,
 };
 
 // ---------------------------------------------------------------------------
@@ -3231,6 +3234,11 @@ struct sre_ctx {
     // storage merge ran, [5] rows captured for the next call. Reset with
     // path_cnt; filled by incremental_root_impl.
     uint64_t inc_cnt[6] = {0, 0, 0, 0, 0, 0};
+    // hash-and-sort counters of the last plain-state upload that installed a
+    // state (sre_get_hash_sort_counters): [0] keccak-f invocations, [1] radix
+    // passes executed, [2] passes skipped, [3] rows in tie runs, [4] tie
+    // runs, [5] address hashes reused (always 0: not built).
+    uint64_t hs_cnt[6] = {0, 0, 0, 0, 0, 0};
     // TrieUpdates retention (sre_root_with_updates)
     bool retain_updates = false;
     std::vector<sre_update_row> updates;
@@ -4359,6 +4367,10 @@ static int fail_flags(sre_ctx *ctx, uint32_t e)
         msg += " storage-for-unknown-account";
     if (e & (1u << E_ZERO_VALUE))
         msg += " zero-storage-value";
+    if (e & (1u << E_DUP_ADDRESS))
+        msg += " duplicate-address";
+    if (e & (1u << E_DUP_STORAGE))
+        msg += " duplicate-storage-slot";
     if (e & (1u << E_INTERNAL))
         msg += " internal-group-invariant";
     set_err(ctx, msg);
@@ -6427,5 +6439,617 @@ extern "C" int sre_get_path_counters(sre_ctx *ctx, uint64_t out[4])
 extern "C" int sre_get_incremental_counters(sre_ctx *ctx, uint64_t out[6])
 {
     memcpy(out, ctx->inc_cnt, sizeof(ctx->inc_cnt));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// plain-state upload (sre_upload_plain_state / sre_set_plain_state_device):
+// hash addresses and slots, sort by hashed key, install as resident state.
+// The device half of reth's AccountHashingStage / StorageHashingStage and of
+// HashedPostState::from_bundle_state + into_sorted. Arithmetic shared with
+// the host check lives in radix.h; DESIGN.md §14 has the reasoning.
+// ---------------------------------------------------------------------------
+
+#define PLAIN_ACCT_B 96u  // sizeof(sre_plain_account)
+#define PLAIN_ST_B 84u    // sizeof(sre_plain_storage)
+static_assert(sizeof(sre_plain_account) == PLAIN_ACCT_B, "sre_plain_account");
+static_assert(sizeof(sre_plain_storage) == PLAIN_ST_B, "sre_plain_storage");
+static_assert(HS_WAVES * HS_WAVE == BLOCK, "a tile is sorted by one block");
+
+__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi)
+{
+    return ((uint64_t)hi << 32) | lo;
+}
+
+__device__ __forceinline__ void store_hash(uint8_t *dst, const uint64_t s[25])
+{
+    uint4 *o = (uint4 *)dst;
+    o[0] = make_uint4((uint32_t)s[0], (uint32_t)(s[0] >> 32), (uint32_t)s[1],
+                      (uint32_t)(s[1] >> 32));
+    o[1] = make_uint4((uint32_t)s[2], (uint32_t)(s[2] >> 32), (uint32_t)s[3],
+                      (uint32_t)(s[3] >> 32));
+}
+
+// keccak256 of a 20-byte address given as five LE dwords: the single block
+// is composed in registers (pad byte 0x01 at offset 20, 0x80 at offset 135).
+__device__ __forceinline__ void keccak_address(uint32_t a0, uint32_t a1, uint32_t a2,
+                                               uint32_t a3, uint32_t a4,
+                                               uint64_t s[25])
+{
+#pragma unroll
+    for (int k = 0; k < 25; ++k)
+        s[k] = 0;
+    s[0] = u64_of(a0, a1);
+    s[1] = u64_of(a2, a3);
+    s[2] = u64_of(a4, 0x01u);
+    s[16] = 0x8000000000000000ull;
+    keccak_f(s);
+}
+
+// One lane per plain account row: hashed address (32 B), sort key, row index.
+__global__ void __launch_bounds__(BLOCK) k_hs_account_keys(
+    const uint8_t *__restrict__ plain, uint64_t na, int keep,
+    uint8_t *__restrict__ hk, uint64_t *__restrict__ keys,
+    uint32_t *__restrict__ idx)
+{
+    uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= na)
+        return;
+    const uint8_t *row = plain + i * PLAIN_ACCT_B; // 16-B aligned
+    uint4 a = *(const uint4 *)row;
+    uint32_t a4 = *(const uint32_t *)(row + 16);
+    uint64_t s[25];
+    keccak_address(a.x, a.y, a.z, a.w, a4, s);
+    store_hash(hk + i * 32, s);
+    keys[i] = hs_account_key(s[0], keep);
+    idx[i] = (uint32_t)i;
+}
+
+// One lane per plain storage row: hash the address, find its rank in the
+// sorted accounts (a miss is an orphan row), hash the slot, emit the hashed
+// slot key, the (rank, slot prefix) sort key and the row index.
+__global__ void __launch_bounds__(BLOCK) k_hs_storage_keys(
+    const uint8_t *__restrict__ plain, uint64_t ns,
+    const sre_account_entry *__restrict__ acct, uint64_t na, int keep,
+    uint8_t *__restrict__ hks, uint64_t *__restrict__ keys,
+    uint32_t *__restrict__ idx, uint32_t *__restrict__ err)
+{
+    uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= ns)
+        return;
+    const uint32_t *row = (const uint32_t *)(plain + i * PLAIN_ST_B); // 4-B aligned
+    uint64_t s[25];
+    keccak_address(row[0], row[1], row[2], row[3], row[4], s);
+    uint64_t h[4] = {s[0], s[1], s[2], s[3]};
+    uint64_t lo = 0, hi = na;
+    while (lo < hi) {
+        uint64_t mid = (lo + hi) / 2;
+        const uint64_t *k = (const uint64_t *)&acct[mid];
+        uint64_t w[4] = {k[0], k[1], k[2], k[3]};
+        if (hs_cmp_words(w, h) < 0)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    bool found = false;
+    if (lo < na) {
+        const uint64_t *k = (const uint64_t *)&acct[lo];
+        uint64_t w[4] = {k[0], k[1], k[2], k[3]};
+        found = hs_cmp_words(w, h) == 0;
+    }
+    if (!found)
+        atomicOr(err, 1u << E_ORPHAN_STORAGE);
+#pragma unroll
+    for (int k = 0; k < 25; ++k)
+        s[k] = 0;
+    s[0] = u64_of(row[5], row[6]);
+    s[1] = u64_of(row[7], row[8]);
+    s[2] = u64_of(row[9], row[10]);
+    s[3] = u64_of(row[11], row[12]);
+    s[4] = 0x01ull;
+    s[16] = 0x8000000000000000ull;
+    keccak_f(s);
+    store_hash(hks + i * 32, s);
+    keys[i] = hs_storage_key(found ? (uint32_t)lo : 0u, s[0], keep);
+    idx[i] = (uint32_t)i;
+}
+
+// hs_sort_pairs stage 1: one tile's 256-bin histogram of digit `pass`, one
+// global write per bin.
+__global__ void __launch_bounds__(BLOCK) k_hs_hist(
+    const uint64_t *__restrict__ keys, uint64_t n, int pass, uint64_t ntiles,
+    uint32_t *__restrict__ hist)
+{
+    __shared__ uint32_t bins[HS_BINS];
+    bins[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t tile = blockIdx.x;
+    const uint32_t wave = threadIdx.x / HS_WAVE, lane = threadIdx.x % HS_WAVE;
+#pragma unroll
+    for (uint32_t r = 0; r < HS_ROUNDS; ++r) {
+        uint64_t i = hs_item_index(tile, wave, r, lane);
+        if (i < n)
+            atomicAdd(&bins[hs_digit(keys[i], pass)], 1u);
+    }
+    __syncthreads();
+    hist[hs_hist_slot(threadIdx.x, tile, ntiles)] = bins[threadIdx.x];
+}
+
+// Skip test on the scanned histogram matrix: a digit that holds all n pairs
+// means the pass would move nothing.
+__global__ void k_hs_one_bin(const uint32_t *__restrict__ offs, uint64_t ntiles,
+                             uint64_t n, uint32_t *__restrict__ flag)
+{
+    uint32_t d = threadIdx.x;
+    uint64_t first = offs[hs_hist_slot(d, 0, ntiles)];
+    uint64_t end = d + 1 < HS_BINS ? offs[hs_hist_slot(d + 1, 0, ntiles)] : n;
+    if (end - first == n)
+        *flag = 1;
+}
+
+// hs_sort_pairs stage 3: stable scatter of one tile. The rank of a pair
+// among the tile's pairs of its digit is built from wave64 peer masks (eight
+// ballots per round) and per-(wave, digit) counters in LDS; see radix.h for
+// the order that makes it stable.
+__global__ void __launch_bounds__(BLOCK) k_hs_scatter(
+    const uint64_t *__restrict__ keys_in, const uint32_t *__restrict__ idx_in,
+    uint64_t n, int pass, uint64_t ntiles, const uint32_t *__restrict__ offs,
+    uint64_t *__restrict__ keys_out, uint32_t *__restrict__ idx_out)
+{
+    __shared__ uint32_t wcount[HS_WAVES][HS_BINS];
+    const uint64_t tile = blockIdx.x;
+    const uint32_t wave = threadIdx.x / HS_WAVE, lane = threadIdx.x % HS_WAVE;
+#pragma unroll
+    for (uint32_t w = 0; w < HS_WAVES; ++w)
+        wcount[w][threadIdx.x] = 0;
+    __syncthreads();
+
+    uint64_t key[HS_ROUNDS], peers[HS_ROUNDS];
+    uint32_t id[HS_ROUNDS];
+#pragma unroll
+    for (uint32_t r = 0; r < HS_ROUNDS; ++r) {
+        uint64_t i = hs_item_index(tile, wave, r, lane);
+        bool valid = i < n;
+        key[r] = valid ? keys_in[i] : 0;
+        id[r] = valid ? idx_in[i] : 0;
+        uint32_t d = hs_digit(key[r], pass);
+        uint64_t p = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < HS_RADIX_BITS; ++b) {
+            bool bit = (d >> b) & 1u;
+            uint64_t m = __ballot(bit);
+            p &= bit ? m : ~m;
+        }
+        peers[r] = valid ? p : 0;
+        // the lowest peer counts the round's pairs of this digit for its wave
+        if (valid && lane == (uint32_t)__builtin_ctzll(p))
+            atomicAdd(&wcount[wave][d], (uint32_t)__popcll(p));
+    }
+    __syncthreads();
+    // per digit: the tile's first slot, then the four waves in order
+    {
+        uint32_t d = threadIdx.x;
+        uint32_t g = offs[hs_hist_slot(d, tile, ntiles)];
+#pragma unroll
+        for (uint32_t w = 0; w < HS_WAVES; ++w) {
+            uint32_t c = wcount[w][d];
+            wcount[w][d] = g;
+            g += c;
+        }
+    }
+    __syncthreads();
+    // rounds in order: the lowest peer claims the round's slots of its digit
+    // (LDS atomics of one wave complete in issue order, so a later round
+    // sees the earlier rounds' claims) and hands the base to its peers
+#pragma unroll
+    for (uint32_t r = 0; r < HS_ROUNDS; ++r) {
+        uint64_t p = peers[r];
+        bool valid = p != 0;
+        uint32_t d = hs_digit(key[r], pass);
+        uint32_t leader = valid ? (uint32_t)__builtin_ctzll(p) : 0u;
+        uint32_t base = 0;
+        if (valid && lane == leader)
+            base = atomicAdd(&wcount[wave][d], (uint32_t)__popcll(p));
+        base = __shfl(base, (int)leader, HS_WAVE);
+        if (valid) {
+            uint64_t pos = base + hs_rank_in_mask(p, lane);
+            keys_out[pos] = key[r];
+            idx_out[pos] = id[r];
+        }
+    }
+}
+
+// Tie runs = maximal runs of equal adjacent sort keys, length >= 2.
+// cnt[0] += rows inside runs, cnt[1] += runs.
+__global__ void __launch_bounds__(BLOCK) k_hs_tie_count(
+    const uint64_t *__restrict__ keys, uint64_t n, unsigned long long *cnt)
+{
+    uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    bool in = i < n;
+    uint64_t k = in ? keys[i] : 0;
+    bool eqp = in && i > 0 && keys[i - 1] == k;
+    bool eqn = in && i + 1 < n && keys[i + 1] == k;
+    uint64_t rows = __ballot(eqp || eqn), heads = __ballot(eqn && !eqp);
+    if (threadIdx.x % HS_WAVE == 0) {
+        if (rows)
+            atomicAdd(&cnt[0], (unsigned long long)__popcll(rows));
+        if (heads)
+            atomicAdd(&cnt[1], (unsigned long long)__popcll(heads));
+    }
+}
+
+// One thread per run head insertion-sorts the run's row indices by the full
+// 32-byte hashed key (hk[32 * row]); an exact tie keeps row order and raises
+// the duplicate bit. Right for any run length, fast for short ones.
+__global__ void __launch_bounds__(BLOCK) k_hs_tie_sort(
+    const uint64_t *__restrict__ keys, uint32_t *__restrict__ idx, uint64_t n,
+    const uint8_t *__restrict__ hk, uint32_t dup_bit, uint32_t *__restrict__ err)
+{
+    uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n)
+        return;
+    uint64_t k = keys[i];
+    if (i > 0 && keys[i - 1] == k)
+        return;
+    uint64_t end = i + 1;
+    while (end < n && keys[end] == k)
+        ++end;
+    bool dup = false;
+    for (uint64_t a = i + 1; a < end; ++a) {
+        uint32_t v = idx[a];
+        const uint64_t *pv = (const uint64_t *)(hk + (uint64_t)v * 32);
+        uint64_t hv[4] = {pv[0], pv[1], pv[2], pv[3]};
+        uint64_t b = a;
+        while (b > i) {
+            uint32_t u = idx[b - 1];
+            const uint64_t *pu = (const uint64_t *)(hk + (uint64_t)u * 32);
+            uint64_t hu[4] = {pu[0], pu[1], pu[2], pu[3]};
+            int c = hs_cmp_words(hu, hv);
+            if (c == 0) {
+                dup = true;
+                c = u < v ? -1 : 1;
+            }
+            if (c < 0)
+                break;
+            idx[b] = u;
+            --b;
+        }
+        idx[b] = v;
+    }
+    if (dup)
+        atomicOr(err, 1u << dup_bit);
+}
+
+// out[i] = (hashed key, nonce, balance, code_hash) of plain row idx[i].
+// 16-B loads from the 96-B plain rows; the 104-B output stride allows 8 B.
+__global__ void __launch_bounds__(BLOCK) k_hs_gather_accounts(
+    const uint8_t *__restrict__ plain, const uint8_t *__restrict__ hk,
+    const uint32_t *__restrict__ idx, uint64_t na,
+    sre_account_entry *__restrict__ out)
+{
+    uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= na)
+        return;
+    uint64_t src = idx[i];
+    const uint4 *h = (const uint4 *)(hk + src * 32);
+    const uint4 *r = (const uint4 *)(plain + src * PLAIN_ACCT_B);
+    uint4 h0 = h[0], h1 = h[1], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4],
+          r5 = r[5];
+    uint64_t *o = (uint64_t *)&out[i];
+    o[0] = u64_of(h0.x, h0.y);
+    o[1] = u64_of(h0.z, h0.w);
+    o[2] = u64_of(h1.x, h1.y);
+    o[3] = u64_of(h1.z, h1.w);
+    o[4] = u64_of(r1.z, r1.w); // nonce at byte 24
+    o[5] = u64_of(r2.x, r2.y);
+    o[6] = u64_of(r2.z, r2.w);
+    o[7] = u64_of(r3.x, r3.y);
+    o[8] = u64_of(r3.z, r3.w);
+    o[9] = u64_of(r4.x, r4.y);
+    o[10] = u64_of(r4.z, r4.w);
+    o[11] = u64_of(r5.x, r5.y);
+    o[12] = u64_of(r5.z, r5.w);
+}
+
+// out[i] = (account key of the row's rank, hashed slot, value) of plain
+// row idx[i]; flags zero values. The 84-B plain rows allow 4-B loads only;
+// the hashed keys and the 96-B output rows move as 16 B.
+__global__ void __launch_bounds__(BLOCK) k_hs_gather_storage(
+    const uint8_t *__restrict__ plain, const uint8_t *__restrict__ hks,
+    const uint64_t *__restrict__ keys, const uint32_t *__restrict__ idx,
+    uint64_t ns, const sre_account_entry *__restrict__ acct,
+    sre_storage_entry *__restrict__ out, uint32_t *__restrict__ err)
+{
+    uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= ns)
+        return;
+    uint64_t src = idx[i];
+    uint64_t rank = keys[i] >> 32;
+    const uint64_t *ak = (const uint64_t *)&acct[rank];
+    uint64_t a0 = ak[0], a1 = ak[1], a2 = ak[2], a3 = ak[3];
+    const uint4 *h = (const uint4 *)(hks + src * 32);
+    uint4 h0 = h[0], h1 = h[1];
+    const uint32_t *v = (const uint32_t *)(plain + src * PLAIN_ST_B) + 13;
+    uint4 v0 = make_uint4(v[0], v[1], v[2], v[3]);
+    uint4 v1 = make_uint4(v[4], v[5], v[6], v[7]);
+    if (!(v0.x | v0.y | v0.z | v0.w | v1.x | v1.y | v1.z | v1.w))
+        atomicOr(err, 1u << E_ZERO_VALUE);
+    uint4 *o = (uint4 *)&out[i];
+    o[0] = make_uint4((uint32_t)a0, (uint32_t)(a0 >> 32), (uint32_t)a1,
+                      (uint32_t)(a1 >> 32));
+    o[1] = make_uint4((uint32_t)a2, (uint32_t)(a2 >> 32), (uint32_t)a3,
+                      (uint32_t)(a3 >> 32));
+    o[2] = h0;
+    o[3] = h1;
+    o[4] = v0;
+    o[5] = v1;
+}
+
+// Test gate (read per call, inert when unset): keep only the top K bits of
+// the hashed prefix in the sort keys so that ties carry the sort.
+static int hs_key_bits()
+{
+    const char *e = getenv("SRE_HS_KEY_BITS");
+    return e ? atoi(e) : -1;
+}
+
+static int read_u32(sre_ctx *ctx, const uint32_t *d, uint32_t *out)
+{
+    HIP_CHECK(ctx, hipMemcpyAsync(out, d, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// (u64 key, u32 row index) pairs, ping-ponged between two buffer pairs.
+struct hs_pairs {
+    DBuf k[2], x[2];
+    int cur = 0;
+    explicit hs_pairs(sre_ctx *c) : k{DBuf(c), DBuf(c)}, x{DBuf(c), DBuf(c)} {}
+    hipError_t alloc(uint64_t n)
+    {
+        for (int j = 0; j < 2; ++j) {
+            hipError_t e = k[j].alloc(n * 8);
+            if (e == hipSuccess)
+                e = x[j].alloc(n * 4);
+            if (e != hipSuccess)
+                return e;
+        }
+        return hipSuccess;
+    }
+    uint64_t *keys() { return k[cur].as<uint64_t>(); }
+    uint32_t *idx() { return x[cur].as<uint32_t>(); }
+};
+
+// Stable LSD radix sort of n pairs by key, 8-bit digits. Per pass: per-tile
+// histograms, exclusive scan of the [digit][tile] matrix, stable scatter; a
+// pass whose histogram has one bin is skipped. cnt[1] / cnt[2] count the
+// executed / skipped passes. Generic: knows nothing about what a key means.
+static int hs_sort_pairs(sre_ctx *ctx, hs_pairs &pr, uint64_t n, uint64_t cnt[6])
+{
+    if (n == 0)
+        return 0;
+    const uint64_t ntiles = hs_num_tiles(n), cells = ntiles * HS_BINS;
+    DBuf hist(ctx), offs(ctx), flag(ctx);
+    HIP_CHECK(ctx, hist.alloc(cells * 4));
+    HIP_CHECK(ctx, offs.alloc(cells * 4));
+    HIP_CHECK(ctx, flag.alloc(4));
+    for (int pass = 0; pass < HS_PASSES; ++pass) {
+        HIP_CHECK(ctx, hipMemsetAsync(flag.p, 0, 4, ctx->stream));
+        LAUNCH(ctx, k_hs_hist, (uint32_t)ntiles, BLOCK, ctx->stream, pr.keys(), n,
+               pass, ntiles, hist.as<uint32_t>());
+        if (scan_u32(ctx, hist.as<uint32_t>(), offs.as<uint32_t>(), cells, nullptr))
+            return -1;
+        LAUNCH(ctx, k_hs_one_bin, 1, HS_BINS, ctx->stream, offs.as<uint32_t>(),
+               ntiles, n, flag.as<uint32_t>());
+        uint32_t one_bin = 0;
+        if (read_u32(ctx, flag.as<uint32_t>(), &one_bin))
+            return -1;
+        if (one_bin) {
+            cnt[2]++;
+            continue;
+        }
+        LAUNCH(ctx, k_hs_scatter, (uint32_t)ntiles, BLOCK, ctx->stream, pr.keys(),
+               pr.idx(), n, pass, ntiles, offs.as<uint32_t>(),
+               pr.k[pr.cur ^ 1].as<uint64_t>(), pr.x[pr.cur ^ 1].as<uint32_t>());
+        pr.cur ^= 1;
+        cnt[1]++;
+    }
+    return 0;
+}
+
+// Order every tie run of the sorted pairs by the full hashed key.
+static int hs_resolve_ties(sre_ctx *ctx, hs_pairs &pr, uint64_t n, const uint8_t *hk,
+                           uint32_t dup_bit, uint32_t *d_err, uint64_t cnt[6])
+{
+    if (n < 2)
+        return 0;
+    DBuf tc(ctx);
+    HIP_CHECK(ctx, tc.alloc(16));
+    HIP_CHECK(ctx, hipMemsetAsync(tc.p, 0, 16, ctx->stream));
+    LAUNCH(ctx, k_hs_tie_count, grid_for(n), BLOCK, ctx->stream, pr.keys(), n,
+           tc.as<unsigned long long>());
+    unsigned long long h[2] = {0, 0};
+    HIP_CHECK(ctx, hipMemcpyAsync(h, tc.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    cnt[3] += h[0];
+    cnt[4] += h[1];
+    if (h[1])
+        LAUNCH(ctx, k_hs_tie_sort, grid_for(n), BLOCK, ctx->stream, pr.keys(),
+               pr.idx(), n, hk, dup_bit, d_err);
+    return 0;
+}
+
+// A pool buffer that becomes a resident array on success and goes back to
+// the pool otherwise.
+struct hs_out {
+    sre_ctx *ctx;
+    size_t bytes = 0;
+    void *p = nullptr;
+    explicit hs_out(sre_ctx *c) : ctx(c) {}
+    ~hs_out() { pool_put(ctx, bytes, p); }
+    bool alloc(size_t b)
+    {
+        bytes = b;
+        p = pool_get(ctx, b);
+        return p != nullptr;
+    }
+    void *take()
+    {
+        void *q = p;
+        p = nullptr;
+        return q;
+    }
+};
+
+static int plain_state_device(sre_ctx *ctx, const uint8_t *d_pa, uint64_t na,
+                              const uint8_t *d_ps, uint64_t ns)
+{
+    if (check_cap(ctx, na) || check_cap(ctx, ns))
+        return -1;
+    if ((na && !d_pa) || (ns && !d_ps) || ((uintptr_t)d_pa & 15) ||
+        ((uintptr_t)d_ps & 3)) {
+        set_err(ctx, "plain state: null or misaligned row pointer (accounts "
+                     "need 16-byte, storage 4-byte alignment)");
+        return -1;
+    }
+    HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const int keep = hs_key_bits();
+    uint64_t cnt[6] = {na + 2 * ns, 0, 0, 0, 0, 0};
+    DBuf err(ctx);
+    if (alloc_err_flag(ctx, err))
+        return -1;
+    uint32_t *d_err = err.as<uint32_t>();
+
+    // Build into temporaries; the resident state is touched only at the end.
+    hs_out new_acct(ctx), new_st(ctx);
+    if (!new_acct.alloc((na ? na : 1) * sizeof(sre_account_entry)) ||
+        !new_st.alloc((ns ? ns : 1) * sizeof(sre_storage_entry))) {
+        set_err(ctx, "plain state: out of memory (sorted rows)");
+        return -1;
+    }
+    sre_account_entry *acct = (sre_account_entry *)new_acct.p;
+    sre_storage_entry *st = (sre_storage_entry *)new_st.p;
+
+    if (na) {
+        DBuf hk(ctx);
+        hs_pairs pr(ctx);
+        HIP_CHECK(ctx, hk.alloc(na * 32));
+        HIP_CHECK(ctx, pr.alloc(na));
+        LAUNCH(ctx, k_hs_account_keys, grid_for(na), BLOCK, ctx->stream, d_pa, na,
+               keep, hk.as<uint8_t>(), pr.keys(), pr.idx());
+        if (hs_sort_pairs(ctx, pr, na, cnt) ||
+            hs_resolve_ties(ctx, pr, na, hk.as<uint8_t>(), E_DUP_ADDRESS, d_err, cnt))
+            return -1;
+        LAUNCH(ctx, k_hs_gather_accounts, grid_for(na), BLOCK, ctx->stream, d_pa,
+               hk.as<uint8_t>(), pr.idx(), na, acct);
+        if (check_err(ctx, d_err))
+            return -1;
+    }
+    if (ns) {
+        DBuf hks(ctx);
+        hs_pairs pr(ctx);
+        HIP_CHECK(ctx, hks.alloc(ns * 32));
+        HIP_CHECK(ctx, pr.alloc(ns));
+        LAUNCH(ctx, k_hs_storage_keys, grid_for(ns), BLOCK, ctx->stream, d_ps, ns,
+               (const sre_account_entry *)acct, na, keep, hks.as<uint8_t>(),
+               pr.keys(), pr.idx(), d_err);
+        if (check_err(ctx, d_err)) // an orphan row has no rank to sort by
+            return -1;
+        if (hs_sort_pairs(ctx, pr, ns, cnt) ||
+            hs_resolve_ties(ctx, pr, ns, hks.as<uint8_t>(), E_DUP_STORAGE, d_err, cnt))
+            return -1;
+        LAUNCH(ctx, k_hs_gather_storage, grid_for(ns), BLOCK, ctx->stream, d_ps,
+               hks.as<uint8_t>(), pr.keys(), pr.idx(), ns,
+               (const sre_account_entry *)acct, st, d_err);
+        if (check_err(ctx, d_err))
+            return -1;
+    }
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+
+    invalidate_retention(ctx);
+    release_acct(ctx);
+    ctx->acct_pool_bytes = new_acct.bytes;
+    ctx->d_acct = (const sre_account_entry *)new_acct.take();
+    ctx->na = na;
+    ctx->own_acct = true;
+    release_st(ctx);
+    ctx->st_pool_bytes = new_st.bytes;
+    ctx->d_st = (const sre_storage_entry *)new_st.take();
+    ctx->ns = ns;
+    ctx->own_st = true;
+    memcpy(ctx->hs_cnt, cnt, sizeof(cnt));
+    return 0;
+}
+
+extern "C" int sre_set_plain_state_device(sre_ctx *ctx, const void *d_acct,
+                                          uint64_t na, const void *d_st, uint64_t ns)
+{
+    return plain_state_device(ctx, (const uint8_t *)d_acct, na,
+                              (const uint8_t *)d_st, ns);
+}
+
+extern "C" int sre_upload_plain_state(sre_ctx *ctx, const sre_plain_account *accounts,
+                                      uint64_t na, const sre_plain_storage *storage,
+                                      uint64_t ns)
+{
+    if (check_cap(ctx, na) || check_cap(ctx, ns))
+        return -1;
+    if ((na && !accounts) || (ns && !storage)) {
+        set_err(ctx, "sre_upload_plain_state: null row pointer");
+        return -1;
+    }
+    HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    DBuf pa(ctx), ps(ctx);
+    if (na) {
+        HIP_CHECK(ctx, pa.alloc(na * PLAIN_ACCT_B));
+        HIP_CHECK(ctx, hipMemcpy(pa.p, accounts, na * PLAIN_ACCT_B,
+                                 hipMemcpyHostToDevice));
+    }
+    if (ns) {
+        HIP_CHECK(ctx, ps.alloc(ns * PLAIN_ST_B));
+        HIP_CHECK(ctx, hipMemcpy(ps.p, storage, ns * PLAIN_ST_B,
+                                 hipMemcpyHostToDevice));
+    }
+    return plain_state_device(ctx, pa.as<uint8_t>(), na, ps.as<uint8_t>(), ns);
+}
+
+extern "C" int sre_resident_counts(sre_ctx *ctx, uint64_t *na, uint64_t *ns)
+{
+    *na = ctx->na;
+    *ns = ctx->ns;
+    return 0;
+}
+
+// Copy a resident array (owned or borrowed) to the host.
+static int download_rows(sre_ctx *ctx, const char *what, const void *d, uint64_t have,
+                         size_t row, void *out, uint64_t n)
+{
+    if (n != have) {
+        set_err(ctx, std::string(what) + ": n = " + std::to_string(n) +
+                         " but " + std::to_string(have) + " rows are resident");
+        return -1;
+    }
+    HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (n)
+        HIP_CHECK(ctx, hipMemcpy(out, d, n * row, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int sre_download_accounts(sre_ctx *ctx, sre_account_entry *out, uint64_t n)
+{
+    return download_rows(ctx, "sre_download_accounts", ctx->d_acct, ctx->na,
+                         sizeof(sre_account_entry), out, n);
+}
+
+extern "C" int sre_download_storage(sre_ctx *ctx, sre_storage_entry *out, uint64_t n)
+{
+    return download_rows(ctx, "sre_download_storage", ctx->d_st, ctx->ns,
+                         sizeof(sre_storage_entry), out, n);
+}
+
+extern "C" int sre_get_hash_sort_counters(sre_ctx *ctx, uint64_t out[6])
+{
+    memcpy(out, ctx->hs_cnt, sizeof(ctx->hs_cnt));
     return 0;
 }

@@ -65,6 +65,22 @@ UPDATE_DTYPE = np.dtype([
 ])
 assert UPDATE_DTYPE.itemsize == 624
 
+# sre_plain_account / sre_plain_storage (include/sre.h): unhashed rows
+PLAIN_ACCOUNT_DTYPE = np.dtype([
+    ("address", np.uint8, 20),
+    ("pad", np.uint8, 4),
+    ("nonce", np.uint64),
+    ("balance", np.uint8, 32),
+    ("code_hash", np.uint8, 32),
+])
+assert PLAIN_ACCOUNT_DTYPE.itemsize == 96
+PLAIN_STORAGE_DTYPE = np.dtype([
+    ("address", np.uint8, 20),
+    ("slot", np.uint8, 32),
+    ("value", np.uint8, 32),
+])
+assert PLAIN_STORAGE_DTYPE.itemsize == 84
+
 
 class SreStats(ctypes.Structure):
     _fields_ = [
@@ -163,6 +179,69 @@ class StateRootEngine:
         self._check(self._lib.sre_set_storage_device(
             ctypes.c_void_p(self._ctx), ctypes.c_void_p(st_u8.data_ptr()),
             st_u8.shape[0]))
+
+    def upload_plain(self, accounts: np.ndarray, storage: np.ndarray):
+        """Replace the resident state by the hashed, sorted form of plain
+        rows (PLAIN_ACCOUNT_DTYPE / PLAIN_STORAGE_DTYPE, any order): the
+        engine hashes addresses and slots and sorts on the device
+        (include/sre.h sre_upload_plain_state)."""
+        assert accounts.dtype == PLAIN_ACCOUNT_DTYPE
+        assert storage.dtype == PLAIN_STORAGE_DTYPE
+        accounts = np.ascontiguousarray(accounts)
+        storage = np.ascontiguousarray(storage)
+        self._check(self._lib.sre_upload_plain_state(
+            ctypes.c_void_p(self._ctx), _np_ptr(accounts),
+            ctypes.c_uint64(len(accounts)), _np_ptr(storage),
+            ctypes.c_uint64(len(storage))))
+        self._keep = []  # the new state is engine-owned
+
+    def set_plain_device_tensors(self, acct_u8, st_u8):
+        """upload_plain from torch GPU tensors: acct (na,96) uint8, st
+        (ns,84) uint8, contiguous, laid out as sre_plain_account /
+        sre_plain_storage. The engine reads them during the call only and
+        keeps no reference. Its kernels run on the engine's own stream:
+        drain torch's first, as in _keccak_device."""
+        import torch
+        assert acct_u8.dtype.itemsize == 1 and acct_u8.is_contiguous()
+        assert st_u8.dtype.itemsize == 1 and st_u8.is_contiguous()
+        assert acct_u8.shape[1] == 96 and st_u8.shape[1] == 84
+        if acct_u8.is_cuda:
+            torch.cuda.synchronize(acct_u8.device)
+        na, ns = acct_u8.shape[0], st_u8.shape[0]
+        self._check(self._lib.sre_set_plain_state_device(
+            ctypes.c_void_p(self._ctx),
+            ctypes.c_void_p(acct_u8.data_ptr() if na else None),
+            ctypes.c_uint64(na),
+            ctypes.c_void_p(st_u8.data_ptr() if ns else None),
+            ctypes.c_uint64(ns)))
+        self._keep = []
+
+    def resident_counts(self):
+        na, ns = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.sre_resident_counts(
+            ctypes.c_void_p(self._ctx), ctypes.byref(na), ctypes.byref(ns)))
+        return na.value, ns.value
+
+    def download(self):
+        """The resident state as (ACCOUNT_DTYPE array, STORAGE_DTYPE array):
+        the sorted hashed rows, whatever made them resident."""
+        na, ns = self.resident_counts()
+        acct = np.zeros(na, dtype=ACCOUNT_DTYPE)
+        st = np.zeros(ns, dtype=STORAGE_DTYPE)
+        self._check(self._lib.sre_download_accounts(
+            ctypes.c_void_p(self._ctx), _np_ptr(acct), ctypes.c_uint64(na)))
+        self._check(self._lib.sre_download_storage(
+            ctypes.c_void_p(self._ctx), _np_ptr(st), ctypes.c_uint64(ns)))
+        return acct, st
+
+    def hash_sort_counters(self) -> dict:
+        """What the last plain upload did (include/sre.h
+        sre_get_hash_sort_counters)."""
+        out = (ctypes.c_uint64 * 6)()
+        self._check(self._lib.sre_get_hash_sort_counters(
+            ctypes.c_void_p(self._ctx), out))
+        return {"keccak_f": out[0], "passes": out[1], "skipped": out[2],
+                "tie_rows": out[3], "tie_runs": out[4], "addr_reused": out[5]}
 
     def release_borrowed(self):
         """Drop the references keeping borrowed device tensors alive
