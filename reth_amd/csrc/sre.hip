@@ -49,7 +49,9 @@
 
 #include "../../include/sre.h"
 #include "junction.h"
+#include "proof_host.h"
 #include "radix.h"
+#include "updates_diff.h"
 
 #define BLOCK 256u
 
@@ -2014,16 +2016,8 @@ __device__ __forceinline__ uint64_t lb_keys(const uint8_t *base, uint64_t stride
 // semantics). A path node for target index ti is exactly the branch group
 // whose member interval contains ti, so per level chunk one thread per
 // target binary-searches the groups and, on containment, copies the
-// assembled branch RLP out of the scratch slot before it is reused.
-struct proof_row {
-    uint32_t target;
-    int16_t d, P;
-    uint32_t br_len;
-    uint32_t s, e;      // member interval (leaf index range)
-    uint8_t key0[32];   // first key of the interval (ext path nibbles)
-    uint8_t rlp[536];
-};
-static_assert(sizeof(proof_row) == 588, "proof_row layout");
+// assembled branch RLP out of the scratch slot before it is reused, into a
+// proof_row (proof_host.h).
 
 // target key -> index in the sorted account array (+ presence flag)
 __global__ void k_proof_ti(const sre_account_entry *__restrict__ acct,
@@ -3194,18 +3188,6 @@ __global__ void k_scan_add(uint32_t *__restrict__ out, uint64_t n,
                            __VA_ARGS__);                                         \
         HIP_CHECK(ctx, hipGetLastError());                                       \
     } while (0)
-
-// One stored row of the CURRENT trie, as (sort key, 64-bit content hash):
-// the retained row-set snapshot that lets the incremental mode emit a NET
-// TrieUpdates diff (upserts/removals) per delta. Content equality by h64
-// (FNV-1a over masks+hashes+root fields; collision odds are ~1e-19 per
-// pair — far below the GPU's own soft-error rate).
-struct snap_row {
-    uint8_t kind, path_len;
-    uint8_t acct_key[32];
-    uint8_t path[32];
-    uint64_t h64;
-};
 
 struct sre_ctx {
     int device = 0;
@@ -4391,377 +4373,162 @@ static const uint8_t EMPTY_ROOT_H[32] = {
 };
 
 // ---------------------------------------------------------------------------
-// account multiproof (sre_account_proof)
+// multiproofs (sre_account_proof / sre_storage_proof). The device side
+// captures each target's path branches during an ordinary pass; the node
+// lists are assembled on the host (proof_host.h).
 // ---------------------------------------------------------------------------
-// Host-side Keccak-256 (FIPS-202 restatement, independent of oracle/) —
-// used only to derive extension-node child references while assembling
-// proof node lists host-side; all bulk hashing stays on the GPU.
-static void h_keccak_f(uint64_t s[25])
-{
-    static const uint64_t RC[24] = {
-        0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808aULL,
-        0x8000000080008000ULL, 0x000000000000808bULL, 0x0000000080000001ULL,
-        0x8000000080008081ULL, 0x8000000000008009ULL, 0x000000000000008aULL,
-        0x0000000000000088ULL, 0x0000000080008009ULL, 0x000000008000000aULL,
-        0x000000008000808bULL, 0x800000000000008bULL, 0x8000000000008089ULL,
-        0x8000000000008003ULL, 0x8000000000008002ULL, 0x8000000000000080ULL,
-        0x000000000000800aULL, 0x800000008000000aULL, 0x8000000080008081ULL,
-        0x8000000000008080ULL, 0x0000000080000001ULL, 0x8000000080008008ULL};
-    static const int ROT[25] = {0,  1,  62, 28, 27, 36, 44, 6,  55, 20, 3, 10, 43,
-                                25, 39, 41, 45, 15, 21, 8,  18, 2,  61, 56, 14};
-    auto rotl = [](uint64_t v, int r) {
-        return r ? (v << r) | (v >> (64 - r)) : v;
-    };
-    for (int r = 0; r < 24; ++r) {
-        uint64_t c[5], dd[5], b[25];
-        for (int x = 0; x < 5; ++x)
-            c[x] = s[x] ^ s[x + 5] ^ s[x + 10] ^ s[x + 15] ^ s[x + 20];
-        for (int x = 0; x < 5; ++x)
-            dd[x] = c[(x + 4) % 5] ^ rotl(c[(x + 1) % 5], 1);
-        for (int i = 0; i < 25; ++i)
-            s[i] ^= dd[i % 5];
-        for (int x = 0; x < 5; ++x)
-            for (int y = 0; y < 5; ++y)
-                b[y + 5 * ((2 * x + 3 * y) % 5)] = rotl(s[x + 5 * y],
-                                                        ROT[x + 5 * y]);
-        for (int y = 0; y < 5; ++y)
-            for (int x = 0; x < 5; ++x)
-                s[x + 5 * y] = b[x + 5 * y] ^
-                               ((~b[(x + 1) % 5 + 5 * y]) &
-                                b[(x + 2) % 5 + 5 * y]);
-        s[0] ^= RC[r];
-    }
-}
-
-static void h_keccak256(const uint8_t *msg, size_t len, uint8_t out[32])
-{
-    uint64_t s[25] = {0};
-    uint8_t blk[136];
-    size_t off = 0;
-    while (len - off >= 136) {
-        memcpy(blk, msg + off, 136);
-        for (int i = 0; i < 17; ++i) {
-            uint64_t w;
-            memcpy(&w, blk + 8 * i, 8);
-            s[i] ^= w;
-        }
-        h_keccak_f(s);
-        off += 136;
-    }
-    memset(blk, 0, 136);
-    memcpy(blk, msg + off, len - off);
-    blk[len - off] = 0x01;
-    blk[135] |= 0x80;
-    for (int i = 0; i < 17; ++i) {
-        uint64_t w;
-        memcpy(&w, blk + 8 * i, 8);
-        s[i] ^= w;
-    }
-    h_keccak_f(s);
-    memcpy(out, s, 32);
-}
-
-static inline int h_nib(const uint8_t *key, int i)
-{
-    return (i & 1) ? (key[i >> 1] & 0xF) : (key[i >> 1] >> 4);
-}
-
-// RLP string item of the hex-prefix-encoded path key[from..to) (HP per the
-// yellow paper; in-repo shape proof_v2/node.rs:30-68). Returns bytes written.
-static int h_hp_item(uint8_t *dst, const uint8_t *key, int from, int to,
-                     int leaf)
-{
-    int n = to - from;
-    int hl = 1 + n / 2;
-    uint8_t hp[34];
-    int odd = n & 1;
-    hp[0] = (uint8_t)((leaf ? 0x20 : 0x00) | (odd ? 0x10 | h_nib(key, from) : 0));
-    int p = 1, i = from + odd;
-    for (; i < to; i += 2)
-        hp[p++] = (uint8_t)((h_nib(key, i) << 4) | h_nib(key, i + 1));
-    int w = 0;
-    if (hl == 1 && hp[0] < 0x80) {
-        dst[w++] = hp[0];
-    } else {
-        dst[w++] = (uint8_t)(0x80 + hl);
-        memcpy(dst + w, hp, hl);
-        w += hl;
-    }
-    return w;
-}
-
-// RLP of a big-endian unsigned integer (nonce / balance), minimal form.
-static int h_rlp_uint(uint8_t *dst, const uint8_t *be, int len)
-{
-    int s = 0;
-    while (s < len && be[s] == 0)
-        s++;
-    int n = len - s;
-    if (n == 0) {
-        dst[0] = 0x80;
-        return 1;
-    }
-    if (n == 1 && be[s] < 0x80) {
-        dst[0] = be[s];
-        return 1;
-    }
-    dst[0] = (uint8_t)(0x80 + n);
-    memcpy(dst + 1, be + s, n);
-    return 1 + n;
-}
-
-static int h_rlp_list_hdr(uint8_t *dst, int payload)
-{
-    if (payload < 56) {
-        dst[0] = (uint8_t)(0xc0 + payload);
-        return 1;
-    }
-    dst[0] = 0xf8;
-    dst[1] = (uint8_t)payload;
-    return 2;
-}
-
-// Account leaf node RLP: [HP(short,1), RLP_string(RLP([nonce,balance,
-// storage_root,code_hash]))] (trie.rs:472-476; proof_v2/value.rs:55-139).
-static int h_leaf_node(uint8_t *dst, const uint8_t *key, int from,
-                       const sre_account_entry *a,
-                       const uint8_t storage_root[32])
-{
-    uint8_t val[120];
-    uint8_t nb[8];
-    for (int i = 0; i < 8; ++i)
-        nb[i] = (uint8_t)(a->nonce >> (8 * (7 - i)));
-    int vp = 0;
-    uint8_t body[112];
-    int bp = 0;
-    bp += h_rlp_uint(body + bp, nb, 8);
-    bp += h_rlp_uint(body + bp, a->balance, 32);
-    body[bp++] = 0xa0;
-    memcpy(body + bp, storage_root, 32);
-    bp += 32;
-    body[bp++] = 0xa0;
-    memcpy(body + bp, a->code_hash, 32);
-    bp += 32;
-    vp += h_rlp_list_hdr(val + vp, bp);
-    memcpy(val + vp, body, bp);
-    vp += bp;
-    // leaf list: [hp, value-as-string]
-    uint8_t hp[40];
-    int hl = h_hp_item(hp, key, from, 64, 1);
-    int pay = hl + (vp < 56 ? 1 : 2) + vp;
-    int w = h_rlp_list_hdr(dst, pay);
-    memcpy(dst + w, hp, hl);
-    w += hl;
-    if (vp < 56) {
-        dst[w++] = (uint8_t)(0x80 + vp);
-    } else {
-        dst[w++] = 0xb8;
-        dst[w++] = (uint8_t)vp;
-    }
-    memcpy(dst + w, val, vp);
-    return w + vp;
-}
-
-// ---- proof assembly: RLP list parser + semantic walk -----------------
-// The emitted proof is exactly the node chain a verifier walks from the
-// root by the target's nibbles (eth_getProof / ProofRetainer semantics):
-// present keys end at the target leaf, absent keys end at the first
-// divergence (empty branch slot, mismatching extension/leaf path). Inline
-// (<32 B) nodes are traversed in place and never emitted.
-struct h_item {
-    const uint8_t *pay;
-    int len;
-    bool is_list;
-    const uint8_t *raw;
-    int raw_len;
+// Target keys -> index in a resident sorted array + presence flag: 32-byte
+// keys against the accounts, 64-byte (account || slot) pairs against the
+// storage rows.
+struct proof_lookup {
+    uint32_t n = 0;
+    DBuf dkeys, dti, dpres;
+    std::vector<uint32_t> ti, pres;
+    explicit proof_lookup(sre_ctx *c) : dkeys(c), dti(c), dpres(c) {}
 };
 
-static int h_rlp_list_items(const uint8_t *b, int len, std::vector<h_item> &out)
+static int proof_lookup_launch(sre_ctx *ctx, proof_lookup &l,
+                               const uint8_t *keys, uint32_t klen, uint32_t n_t)
 {
-    if (len < 1 || b[0] < 0xc0)
-        return -1;
-    int pl, off;
-    if (b[0] < 0xf8) {
-        pl = b[0] - 0xc0;
-        off = 1;
-    } else {
-        int n = b[0] - 0xf7;
-        pl = 0;
-        for (int k = 0; k < n; ++k)
-            pl = (pl << 8) | b[1 + k];
-        off = 1 + n;
-    }
-    if (off + pl != len)
-        return -1;
-    int i = off, end = off + pl;
-    while (i < end) {
-        uint8_t c = b[i];
-        h_item it{};
-        if (c < 0x80) {
-            it.pay = b + i;
-            it.len = 1;
-            i += 1;
-        } else if (c < 0xb8) {
-            it.pay = b + i + 1;
-            it.len = c - 0x80;
-            i += 1 + it.len;
-        } else if (c < 0xc0) {
-            int n = c - 0xb7;
-            int ln = 0;
-            for (int k = 0; k < n; ++k)
-                ln = (ln << 8) | b[i + 1 + k];
-            it.pay = b + i + 1 + n;
-            it.len = ln;
-            i += 1 + n + ln;
-        } else {
-            int hn, ln;
-            if (c < 0xf8) {
-                hn = 1;
-                ln = c - 0xc0;
-            } else {
-                hn = 1 + (c - 0xf7);
-                ln = 0;
-                for (int k = 0; k < hn - 1; ++k)
-                    ln = (ln << 8) | b[i + 1 + k];
-            }
-            it.is_list = true;
-            it.raw = b + i;
-            it.raw_len = hn + ln;
-            i += hn + ln;
-        }
-        if (i > end)
-            return -1;
-        out.push_back(it);
-    }
+    l.n = n_t;
+    HIP_CHECK(ctx, l.dkeys.alloc((uint64_t)klen * n_t));
+    HIP_CHECK(ctx, hipMemcpyAsync(l.dkeys.p, keys, (uint64_t)klen * n_t,
+                                  hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(ctx, l.dti.alloc(4ull * n_t));
+    HIP_CHECK(ctx, l.dpres.alloc(4ull * n_t));
+    if (klen == 32)
+        LAUNCH(ctx, k_proof_ti, grid_for(n_t), BLOCK, ctx->stream, ctx->d_acct,
+               ctx->na, l.dkeys.as<uint8_t>(), n_t, l.dti.as<uint32_t>(),
+               l.dpres.as<uint32_t>());
+    else
+        LAUNCH(ctx, k_proof_ti64, grid_for(n_t), BLOCK, ctx->stream, ctx->d_st,
+               ctx->ns, l.dkeys.as<uint8_t>(), n_t, l.dti.as<uint32_t>(),
+               l.dpres.as<uint32_t>());
     return 0;
 }
 
-typedef std::array<uint8_t, 32> hkey;
-typedef std::map<hkey, std::pair<const uint8_t *, int>> node_map;
-
-// returns 0 = reached the target leaf (present), 1 = divergence proven
-// (absent), -1 = internal error. Emits each hash-referenced node visited.
-template <typename EmitFn>
-static int proof_walk_emit(sre_ctx *ctx, const uint8_t root[32],
-                           const node_map &byhash, const uint8_t *key,
-                           EmitFn &&emit)
+static int proof_lookup_fetch(sre_ctx *ctx, proof_lookup &l)
 {
-    uint8_t nib[64];
-    for (int k = 0; k < 32; ++k) {
-        nib[2 * k] = key[k] >> 4;
-        nib[2 * k + 1] = key[k] & 0xF;
-    }
-    hkey rk;
-    memcpy(rk.data(), root, 32);
-    auto it = byhash.find(rk);
-    if (it == byhash.end()) {
-        set_err(ctx, "proof: root node missing from capture");
-        return -1;
-    }
-    const uint8_t *cur = it->second.first;
-    int clen = it->second.second;
-    bool emit_cur = true;
-    int pos = 0;
-    for (int guard = 0; guard < 200; ++guard) {
-        if (emit_cur && emit(cur, clen))
-            return -1;
-        std::vector<h_item> items;
-        if (h_rlp_list_items(cur, clen, items)) {
-            set_err(ctx, "proof: malformed node");
-            return -1;
-        }
-        const h_item *next = nullptr;
-        if (items.size() == 17) {
-            if (pos >= 64) {
-                set_err(ctx, "proof: branch below leaf depth");
-                return -1;
-            }
-            const h_item &c = items[nib[pos]];
-            if (!c.is_list && c.len == 0)
-                return 1; // empty child slot: absence proven
-            pos++;
-            next = &c;
-        } else if (items.size() == 2) {
-            const uint8_t *hp = items[0].pay;
-            int hl = items[0].len;
-            int flag = hp[0] >> 4;
-            bool is_leaf = (flag & 2) != 0;
-            int np = (hl - 1) * 2 + ((flag & 1) ? 1 : 0);
-            bool match = pos + np <= 64;
-            for (int k = 0; match && k < np; ++k) {
-                int v = ((flag & 1) == 0)
-                            ? ((k & 1) ? hp[1 + k / 2] & 0xF
-                                       : hp[1 + k / 2] >> 4)
-                            : (k == 0 ? hp[0] & 0xF
-                                      : ((k & 1) ? hp[1 + (k - 1) / 2] >> 4
-                                                 : hp[1 + (k - 1) / 2] & 0xF));
-                match = v == nib[pos + k];
-            }
-            if (!match)
-                return 1; // path mismatch: absence proven
-            pos += np;
-            if (is_leaf) {
-                if (pos != 64) {
-                    set_err(ctx, "proof: leaf at wrong depth");
-                    return -1;
-                }
-                return 0; // target leaf reached
-            }
-            next = &items[1];
-        } else {
-            set_err(ctx, "proof: unexpected node arity");
-            return -1;
-        }
-        if (!next->is_list && next->len == 32) {
-            hkey k;
-            memcpy(k.data(), next->pay, 32);
-            auto jt = byhash.find(k);
-            if (jt == byhash.end()) {
-                set_err(ctx, "proof: child node missing from capture");
-                return -1;
-            }
-            cur = jt->second.first;
-            clen = jt->second.second;
-            emit_cur = true;
-        } else { // inline embedded node: traverse, do not emit
-            cur = next->is_list ? next->raw : next->pay;
-            clen = next->is_list ? next->raw_len : next->len;
-            emit_cur = false;
-        }
-    }
-    set_err(ctx, "proof: walk did not terminate");
-    return -1;
+    l.ti.resize(l.n);
+    l.pres.resize(l.n);
+    HIP_CHECK(ctx, hipMemcpy(l.ti.data(), l.dti.p, 4ull * l.n,
+                             hipMemcpyDeviceToHost));
+    HIP_CHECK(ctx, hipMemcpy(l.pres.data(), l.dpres.p, 4ull * l.n,
+                             hipMemcpyDeviceToHost));
+    return 0;
 }
 
-// build the ext-wrapper bytes for a captured row (path nibbles from the
-// row's own first key — valid for on-path and sibling rows alike)
-static void h_row_ext(const proof_row *r, std::vector<uint8_t> &out)
-{
-    uint8_t cref[33];
-    int crl;
-    if (r->br_len >= 32) {
-        cref[0] = 0xa0;
-        h_keccak256(r->rlp, r->br_len, cref + 1);
-        crl = 33;
-    } else {
-        memcpy(cref, r->rlp, r->br_len);
-        crl = (int)r->br_len;
-    }
-    uint8_t hp[40];
-    int hl = h_hp_item(hp, r->key0, r->P + 1, r->d, 0);
-    out.resize(2 + hl + crl);
-    int w = h_rlp_list_hdr(out.data(), hl + crl);
-    memcpy(out.data() + w, hp, hl);
-    memcpy(out.data() + w + hl, cref, crl);
-    out.resize(w + hl + crl);
-}
+// What both proof calls do around their pass: arm() sets up the row capture
+// for the looked-up targets, collect() brings the captured rows back grouped
+// per target, emit() assembles one target's proof into the caller's buffers.
+struct proof_call {
+    sre_ctx *ctx;
+    const std::string name; // the entry point, for its error messages
+    const std::string full = name + ": output capacity exceeded";
+    DBuf err, acct_roots; // the pass's error flag and storage roots
+    proof_lookup tgt;
+    DBuf dti2, drows, dcount;
+    proof_capture cap;
+    std::vector<proof_row> rows;
+    std::vector<std::vector<const proof_row *>> per; // root-first
+    proof_sink out;
 
-static void map_add(node_map &m, const uint8_t *b, int len)
-{
-    hkey k;
-    h_keccak256(b, len, k.data());
-    m.emplace(k, std::make_pair(b, len));
-}
+    proof_call(sre_ctx *c, const char *fn, uint8_t *out_nodes,
+               uint64_t cap_nodes, uint32_t *out_lens, uint64_t cap_lens)
+        : ctx(c), name(fn), err(c), acct_roots(c), tgt(c), dti2(c), drows(c),
+          dcount(c),
+          out{out_nodes, cap_nodes, out_lens, cap_lens, full.c_str()}
+    {
+    }
+
+    int begin()
+    {
+        if (alloc_err_flag(ctx, err))
+            return -1;
+        HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
+        return 0;
+    }
+
+    int arm()
+    {
+        uint32_t n_t = tgt.n;
+        // exclusion targets also need the LEFT neighbour's path: a target
+        // that sorts after every key of the divergent subtree has its lookup
+        // path under index ti-1, not ti
+        HIP_CHECK(ctx, dti2.alloc(4ull * n_t));
+        {
+            std::vector<uint32_t> ti2(n_t);
+            for (uint32_t t = 0; t < n_t; ++t)
+                ti2[t] = (!tgt.pres[t] && tgt.ti[t] > 0) ? tgt.ti[t] - 1
+                                                         : tgt.ti[t];
+            HIP_CHECK(ctx, hipMemcpyAsync(dti2.p, ti2.data(), 4ull * n_t,
+                                          hipMemcpyHostToDevice, ctx->stream));
+        }
+        uint32_t cap_rows = n_t * 260 + 64;
+        HIP_CHECK(ctx, drows.alloc((uint64_t)cap_rows * sizeof(proof_row)));
+        HIP_CHECK(ctx, dcount.alloc(4));
+        HIP_CHECK(ctx, hipMemsetAsync(dcount.p, 0, 4, ctx->stream));
+        cap.pti = tgt.dti.as<uint32_t>();
+        cap.pti2 = dti2.as<uint32_t>();
+        cap.n = n_t;
+        cap.rows = drows.as<proof_row>();
+        cap.row_count = dcount.as<uint32_t>();
+        cap.row_cap = cap_rows;
+        return 0;
+    }
+
+    int collect()
+    {
+        if (check_err(ctx, err.as<uint32_t>()))
+            return -1;
+        uint32_t nrows = 0;
+        HIP_CHECK(ctx, hipMemcpy(&nrows, dcount.p, 4, hipMemcpyDeviceToHost));
+        rows.resize(nrows);
+        if (nrows)
+            HIP_CHECK(ctx, hipMemcpy(rows.data(), drows.p,
+                                     (uint64_t)nrows * sizeof(proof_row),
+                                     hipMemcpyDeviceToHost));
+        per.resize(tgt.n);
+        for (const auto &r : rows)
+            per[r.target].push_back(&r);
+        for (auto &v : per)
+            std::sort(v.begin(), v.end(),
+                      [](const proof_row *a, const proof_row *b) {
+                          return a->d < b->d;
+                      });
+        return 0;
+    }
+
+    // nibble at which the leaf at entry index idx starts on target t's path:
+    // one below the deepest captured branch that has idx among its members
+    int leaf_from(uint32_t t, uint32_t idx) const
+    {
+        int dmax = -1;
+        for (const proof_row *r : per[t])
+            if (r->s <= idx && idx < r->e && r->d > dmax)
+                dmax = r->d;
+        return dmax + 1;
+    }
+
+    int emit(uint32_t t, const uint8_t root[32], const uint8_t *key,
+             const std::vector<std::vector<uint8_t>> &leaves,
+             uint32_t *out_counts)
+    {
+        uint32_t cnt = 0;
+        const char *why = nullptr;
+        int rc = proof_assemble(root, key, per[t], leaves, out, &cnt, &why);
+        if (rc < 0) {
+            set_err(ctx, why);
+            return -1;
+        }
+        if ((rc == 0) != (tgt.pres[t] != 0)) {
+            set_err(ctx, name + ": internal presence mismatch");
+            return -1;
+        }
+        out_counts[t] = cnt;
+        return 0;
+    }
+};
 
 extern "C" int sre_account_proof(sre_ctx *ctx, const uint8_t *targets,
                                  uint64_t n_targets, uint8_t *out_nodes,
@@ -4780,105 +4547,41 @@ extern "C" int sre_account_proof(sre_ctx *ctx, const uint8_t *targets,
         return 0;
     }
     uint32_t n_t = (uint32_t)n_targets;
-    DBuf err(ctx), acct_roots(ctx), root(ctx), dtgt(ctx), dti(ctx), dpres(ctx),
-        prows(ctx), prowc(ctx);
-    if (alloc_err_flag(ctx, err))
+    proof_call pc(ctx, "sre_account_proof", out_nodes, cap_nodes, out_lens,
+                  cap_lens);
+    DBuf root(ctx);
+    if (pc.begin())
         return -1;
-    HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
     HIP_CHECK(ctx, root.alloc(32));
-    HIP_CHECK(ctx, dtgt.alloc(32ull * n_t));
-    HIP_CHECK(ctx, hipMemcpyAsync(dtgt.p, targets, 32ull * n_t,
-                                  hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(ctx, dti.alloc(4ull * n_t));
-    HIP_CHECK(ctx, dpres.alloc(4ull * n_t));
-    LAUNCH(ctx, k_proof_ti, grid_for(n_t), BLOCK, ctx->stream, ctx->d_acct,
-           ctx->na, dtgt.as<uint8_t>(), n_t, dti.as<uint32_t>(),
-           dpres.as<uint32_t>());
-    std::vector<uint32_t> ti(n_t), pres(n_t);
-    HIP_CHECK(ctx, hipMemcpy(ti.data(), dti.p, 4ull * n_t,
-                             hipMemcpyDeviceToHost));
-    HIP_CHECK(ctx, hipMemcpy(pres.data(), dpres.p, 4ull * n_t,
-                             hipMemcpyDeviceToHost));
-    // exclusion targets also need the LEFT neighbour's path: a target that
-    // sorts after every key of the divergent subtree has its lookup path
-    // under index ti-1, not ti
-    DBuf dti2(ctx);
-    HIP_CHECK(ctx, dti2.alloc(4ull * n_t));
-    {
-        std::vector<uint32_t> ti2(n_t);
-        for (uint32_t t = 0; t < n_t; ++t)
-            ti2[t] = (!pres[t] && ti[t] > 0) ? ti[t] - 1 : ti[t];
-        HIP_CHECK(ctx, hipMemcpyAsync(dti2.p, ti2.data(), 4ull * n_t,
-                                      hipMemcpyHostToDevice, ctx->stream));
-    }
-    uint32_t cap_rows = n_t * 260 + 64;
-    HIP_CHECK(ctx, prows.alloc((uint64_t)cap_rows * sizeof(proof_row)));
-    HIP_CHECK(ctx, prowc.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(prowc.p, 0, 4, ctx->stream));
+    if (proof_lookup_launch(ctx, pc.tgt, targets, 32, n_t) ||
+        proof_lookup_fetch(ctx, pc.tgt) || pc.arm())
+        return -1;
+    uint8_t *acct_roots = pc.acct_roots.as<uint8_t>();
+    uint32_t *d_err = pc.err.as<uint32_t>();
 
+    // the capture rides on the account pass
     pass_out po;
-    if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &po, err.as<uint32_t>()))
+    if (run_storage_pass(ctx, acct_roots, &po, d_err))
         return -1;
-    proof_capture proof;
-    proof.pti = dti.as<uint32_t>();
-    proof.pti2 = dti2.as<uint32_t>();
-    proof.n = n_t;
-    proof.rows = prows.as<proof_row>();
-    proof.row_count = prowc.as<uint32_t>();
-    proof.row_cap = cap_rows;
-    if (run_account_pass(ctx, acct_roots.as<uint8_t>(), 0, root.as<uint8_t>(),
-                         nullptr, nullptr, &po, err.as<uint32_t>(),
-                         cell_capture{}, proof))
+    if (run_account_pass(ctx, acct_roots, 0, root.as<uint8_t>(), nullptr,
+                         nullptr, &po, d_err, cell_capture{}, pc.cap))
         return -1;
-    if (check_err(ctx, err.as<uint32_t>()))
+    if (pc.collect())
         return -1;
-    uint32_t nrows = 0;
-    HIP_CHECK(ctx, hipMemcpy(&nrows, prowc.p, 4, hipMemcpyDeviceToHost));
-    std::vector<proof_row> rows(nrows);
-    if (nrows)
-        HIP_CHECK(ctx, hipMemcpy(rows.data(), prows.p,
-                                 (uint64_t)nrows * sizeof(proof_row),
-                                 hipMemcpyDeviceToHost));
     uint8_t engine_root[32];
     HIP_CHECK(ctx, hipMemcpy(engine_root, root.p, 32, hipMemcpyDeviceToHost));
 
-    // per-target path rows, root-first (ascending branch depth)
-    std::vector<std::vector<const proof_row *>> per(n_t);
-    for (const auto &r : rows)
-        per[r.target].push_back(&r);
-    for (auto &v : per)
-        std::sort(v.begin(), v.end(),
-                  [](const proof_row *a, const proof_row *b) {
-                      return a->d < b->d;
-                  });
-
-    uint64_t nb = 0, nl = 0;
+    const std::vector<uint32_t> &ti = pc.tgt.ti, &pres = pc.tgt.pres;
     for (uint32_t t = 0; t < n_t; ++t) {
-        const uint8_t *key = targets + 32ull * t;
-        // node universe for this target: captured branches, their ext
-        // wrappers, and the candidate leaves at ti / ti-1
-        node_map byhash;
-        std::vector<std::vector<uint8_t>> owned;
-        owned.reserve(2 * per[t].size() + 2);
-        for (const proof_row *r : per[t]) {
-            map_add(byhash, r->rlp, (int)r->br_len);
-            if (r->d > r->P + 1) {
-                owned.emplace_back();
-                h_row_ext(r, owned.back());
-                map_add(byhash, owned.back().data(), (int)owned.back().size());
-            }
-        }
+        // candidate leaves: the accounts at ti / ti-1
         uint32_t cands[2];
         int ncand = 0;
         cands[ncand++] = ti[t] < ctx->na ? ti[t] : (uint32_t)(ctx->na - 1);
         if (!pres[t] && ti[t] > 0 && ti[t] - 1 != cands[0])
             cands[ncand++] = ti[t] - 1;
+        std::vector<std::vector<uint8_t>> leaves;
         for (int c = 0; c < ncand; ++c) {
             uint32_t idx = cands[c];
-            int dmax = -1;
-            for (const proof_row *r : per[t])
-                if (r->s <= idx && idx < r->e && r->d > dmax)
-                    dmax = r->d;
             sre_account_entry ae;
             uint8_t sroot[32];
             HIP_CHECK(ctx,
@@ -4886,58 +4589,16 @@ extern "C" int sre_account_proof(sre_ctx *ctx, const uint8_t *targets,
                                 (const uint8_t *)ctx->d_acct +
                                     (uint64_t)idx * sizeof(sre_account_entry),
                                 sizeof(ae), hipMemcpyDeviceToHost));
-            HIP_CHECK(ctx, hipMemcpy(sroot,
-                                     acct_roots.as<uint8_t>() + 32ull * idx,
-                                     32, hipMemcpyDeviceToHost));
-            owned.emplace_back(200);
-            int ll = h_leaf_node(owned.back().data(), ae.key, dmax + 1, &ae,
-                                 sroot);
-            owned.back().resize(ll);
-            map_add(byhash, owned.back().data(), ll);
+            HIP_CHECK(ctx, hipMemcpy(sroot, acct_roots + 32ull * idx, 32,
+                                     hipMemcpyDeviceToHost));
+            leaves.emplace_back(200);
+            leaves.back().resize(h_leaf_node(leaves.back().data(), ae.key,
+                                             pc.leaf_from(t, idx), &ae, sroot));
         }
-        uint32_t cnt = 0;
-        auto emit = [&](const uint8_t *node, int len) -> int {
-            if (nl >= cap_lens || nb + (uint64_t)len > cap_nodes) {
-                set_err(ctx, "sre_account_proof: output capacity exceeded");
-                return -1;
-            }
-            memcpy(out_nodes + nb, node, len);
-            nb += len;
-            out_lens[nl++] = (uint32_t)len;
-            cnt++;
-            return 0;
-        };
-        int rc = proof_walk_emit(ctx, engine_root, byhash, key, emit);
-        if (rc < 0)
+        if (pc.emit(t, engine_root, targets + 32ull * t, leaves, out_counts))
             return -1;
-        if ((rc == 0) != (pres[t] != 0)) {
-            set_err(ctx, "sre_account_proof: internal presence mismatch");
-            return -1;
-        }
-        out_counts[t] = cnt;
     }
     return 0;
-}
-
-// Storage leaf node RLP: [HP(short,1), RLP_string(RLP(U256 value))]
-// (trie.rs:819-825 encode_fixed_size; proof_v2/value.rs:55).
-static int h_storage_leaf(uint8_t *dst, const uint8_t *slot_key, int from,
-                          const uint8_t value_be[32])
-{
-    uint8_t val[40];
-    int vp = h_rlp_uint(val, value_be, 32);
-    // string-wrap the encoded integer: a single byte < 0x80 stays bare
-    int sh = (vp == 1 && val[0] < 0x80) ? 0 : 1;
-    uint8_t hp[40];
-    int hl = h_hp_item(hp, slot_key, from, 64, 1);
-    int pay = hl + sh + vp;
-    int w = h_rlp_list_hdr(dst, pay);
-    memcpy(dst + w, hp, hl);
-    w += hl;
-    if (sh)
-        dst[w++] = (uint8_t)(0x80 + vp);
-    memcpy(dst + w, val, vp);
-    return w + vp;
 }
 
 /* Storage multiproof: per (acct_key, slot_key) PRESENT pair, the storage
@@ -4966,103 +4627,42 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
         memcpy(pairs.data() + 64ull * t, acct_keys + 32ull * t, 32);
         memcpy(pairs.data() + 64ull * t + 32, slot_keys + 32ull * t, 32);
     }
-    DBuf err(ctx), acct_roots(ctx), dtgt(ctx), dti(ctx), dpres(ctx),
-        dacct(ctx), dtia(ctx), dpra(ctx), prows(ctx), prowc(ctx);
-    if (alloc_err_flag(ctx, err))
+    proof_call pc(ctx, "sre_storage_proof", out_nodes, cap_nodes, out_lens,
+                  cap_lens);
+    proof_lookup owner(ctx); // account indices (for the per-target storage root)
+    if (pc.begin() ||
+        proof_lookup_launch(ctx, pc.tgt, pairs.data(), 64, n_t) ||
+        proof_lookup_launch(ctx, owner, acct_keys, 32, n_t) ||
+        proof_lookup_fetch(ctx, pc.tgt) || proof_lookup_fetch(ctx, owner) ||
+        pc.arm())
         return -1;
-    HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
-    HIP_CHECK(ctx, dtgt.alloc(64ull * n_t));
-    HIP_CHECK(ctx, hipMemcpyAsync(dtgt.p, pairs.data(), 64ull * n_t,
-                                  hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(ctx, dti.alloc(4ull * n_t));
-    HIP_CHECK(ctx, dpres.alloc(4ull * n_t));
-    LAUNCH(ctx, k_proof_ti64, grid_for(n_t), BLOCK, ctx->stream, ctx->d_st,
-           ctx->ns, dtgt.as<uint8_t>(), n_t, dti.as<uint32_t>(),
-           dpres.as<uint32_t>());
-    // account indices (for the per-target storage root)
-    HIP_CHECK(ctx, dacct.alloc(32ull * n_t));
-    HIP_CHECK(ctx, hipMemcpyAsync(dacct.p, acct_keys, 32ull * n_t,
-                                  hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(ctx, dtia.alloc(4ull * n_t));
-    HIP_CHECK(ctx, dpra.alloc(4ull * n_t));
-    LAUNCH(ctx, k_proof_ti, grid_for(n_t), BLOCK, ctx->stream, ctx->d_acct,
-           ctx->na, dacct.as<uint8_t>(), n_t, dtia.as<uint32_t>(),
-           dpra.as<uint32_t>());
-    std::vector<uint32_t> ti(n_t), pres(n_t), tia(n_t), presa(n_t);
-    HIP_CHECK(ctx, hipMemcpy(ti.data(), dti.p, 4ull * n_t,
-                             hipMemcpyDeviceToHost));
-    HIP_CHECK(ctx, hipMemcpy(pres.data(), dpres.p, 4ull * n_t,
-                             hipMemcpyDeviceToHost));
-    HIP_CHECK(ctx, hipMemcpy(tia.data(), dtia.p, 4ull * n_t,
-                             hipMemcpyDeviceToHost));
-    HIP_CHECK(ctx, hipMemcpy(presa.data(), dpra.p, 4ull * n_t,
-                             hipMemcpyDeviceToHost));
-    // absent accounts are NOT an error: storage_multiproof returns
-    // StorageMultiProof::empty() for them (proof/mod.rs storage_multiproof
-    // short-circuits on an empty storage cursor), i.e. EMPTY_ROOT_HASH +
-    // an empty node list — same as a present storage-less account.
-    DBuf dti2(ctx);
-    HIP_CHECK(ctx, dti2.alloc(4ull * n_t));
-    {
-        std::vector<uint32_t> ti2(n_t);
-        for (uint32_t t = 0; t < n_t; ++t)
-            ti2[t] = (!pres[t] && ti[t] > 0) ? ti[t] - 1 : ti[t];
-        HIP_CHECK(ctx, hipMemcpyAsync(dti2.p, ti2.data(), 4ull * n_t,
-                                      hipMemcpyHostToDevice, ctx->stream));
-    }
-    uint32_t cap_rows = n_t * 260 + 64;
-    HIP_CHECK(ctx, prows.alloc((uint64_t)cap_rows * sizeof(proof_row)));
-    HIP_CHECK(ctx, prowc.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(prowc.p, 0, 4, ctx->stream));
 
+    // the capture rides on the storage pass
     pass_out po;
-    proof_capture proof;
-    proof.pti = dti.as<uint32_t>();
-    proof.pti2 = dti2.as<uint32_t>();
-    proof.n = n_t;
-    proof.rows = prows.as<proof_row>();
-    proof.row_count = prowc.as<uint32_t>();
-    proof.row_cap = cap_rows;
-    if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &po, err.as<uint32_t>(),
-                         proof))
+    if (run_storage_pass(ctx, pc.acct_roots.as<uint8_t>(), &po,
+                         pc.err.as<uint32_t>(), pc.cap))
         return -1;
-    if (check_err(ctx, err.as<uint32_t>()))
+    if (pc.collect())
         return -1;
-    uint32_t nrows = 0;
-    HIP_CHECK(ctx, hipMemcpy(&nrows, prowc.p, 4, hipMemcpyDeviceToHost));
-    std::vector<proof_row> rows(nrows);
-    if (nrows)
-        HIP_CHECK(ctx, hipMemcpy(rows.data(), prows.p,
-                                 (uint64_t)nrows * sizeof(proof_row),
-                                 hipMemcpyDeviceToHost));
-    std::vector<std::vector<const proof_row *>> per(n_t);
-    for (const auto &r : rows)
-        per[r.target].push_back(&r);
-    for (auto &v : per)
-        std::sort(v.begin(), v.end(),
-                  [](const proof_row *a, const proof_row *b) {
-                      return a->d < b->d;
-                  });
 
-    uint64_t nb = 0, nl = 0;
-    static const uint8_t EMPTY_ROOT_H2[32] = {
-        0x56, 0xe8, 0x1f, 0x17, 0x1b, 0xcc, 0x55, 0xa6, 0xff, 0x83, 0x45,
-        0xe6, 0x92, 0xc0, 0xf8, 0x6e, 0x5b, 0x48, 0xe0, 0x1b, 0x99, 0x6c,
-        0xad, 0xc0, 0x01, 0x62, 0x2f, 0xb5, 0xe3, 0x63, 0xb4, 0x21};
+    const std::vector<uint32_t> &ti = pc.tgt.ti, &pres = pc.tgt.pres;
     for (uint32_t t = 0; t < n_t; ++t) {
-        const uint8_t *key = slot_keys + 32ull * t;
         uint8_t sroot[32];
-        if (!presa[t]) {
-            // absent account: StorageMultiProof::empty()
-            memcpy(out_roots + 32ull * t, EMPTY_ROOT_H2, 32);
+        // absent accounts are NOT an error: storage_multiproof returns
+        // StorageMultiProof::empty() for them (proof/mod.rs storage_multiproof
+        // short-circuits on an empty storage cursor), i.e. EMPTY_ROOT_HASH +
+        // an empty node list — same as a present storage-less account.
+        if (!owner.pres[t]) {
+            memcpy(out_roots + 32ull * t, EMPTY_ROOT_H, 32);
             out_counts[t] = 0;
             continue;
         }
         HIP_CHECK(ctx, hipMemcpy(sroot,
-                                 acct_roots.as<uint8_t>() + 32ull * tia[t], 32,
-                                 hipMemcpyDeviceToHost));
+                                 pc.acct_roots.as<uint8_t>() +
+                                     32ull * owner.ti[t],
+                                 32, hipMemcpyDeviceToHost));
         memcpy(out_roots + 32ull * t, sroot, 32);
-        if (memcmp(sroot, EMPTY_ROOT_H2, 32) == 0) {
+        if (memcmp(sroot, EMPTY_ROOT_H, 32) == 0) {
             // account has no storage: the empty node list proves absence
             if (pres[t]) {
                 set_err(ctx, "sre_storage_proof: internal presence mismatch");
@@ -5070,17 +4670,6 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
             }
             out_counts[t] = 0;
             continue;
-        }
-        node_map byhash;
-        std::vector<std::vector<uint8_t>> owned;
-        owned.reserve(2 * per[t].size() + 2);
-        for (const proof_row *r : per[t]) {
-            map_add(byhash, r->rlp, (int)r->br_len);
-            if (r->d > r->P + 1) {
-                owned.emplace_back();
-                h_row_ext(r, owned.back());
-                map_add(byhash, owned.back().data(), (int)owned.back().size());
-            }
         }
         // candidate slot leaves at ti / ti-1, guarded to THIS account's
         // segment (a neighbour index may belong to another storage trie)
@@ -5090,6 +4679,7 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
             cands[ncand++] = ti[t];
         if (!pres[t] && ti[t] > 0)
             cands[ncand++] = ti[t] - 1;
+        std::vector<std::vector<uint8_t>> leaves;
         for (int c = 0; c < ncand; ++c) {
             uint32_t idx = cands[c];
             sre_storage_entry se;
@@ -5100,36 +4690,13 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
                                 sizeof(se), hipMemcpyDeviceToHost));
             if (memcmp(se.acct_key, acct_keys + 32ull * t, 32) != 0)
                 continue; // other account's segment
-            int dmax = -1;
-            for (const proof_row *r : per[t])
-                if (r->s <= idx && idx < r->e && r->d > dmax)
-                    dmax = r->d;
-            owned.emplace_back(96);
-            int ll = h_storage_leaf(owned.back().data(), se.slot_key,
-                                    dmax + 1, se.value);
-            owned.back().resize(ll);
-            map_add(byhash, owned.back().data(), ll);
+            leaves.emplace_back(96);
+            leaves.back().resize(h_storage_leaf(leaves.back().data(),
+                                                se.slot_key,
+                                                pc.leaf_from(t, idx), se.value));
         }
-        uint32_t cnt = 0;
-        auto emit = [&](const uint8_t *node, int len) -> int {
-            if (nl >= cap_lens || nb + (uint64_t)len > cap_nodes) {
-                set_err(ctx, "sre_storage_proof: output capacity exceeded");
-                return -1;
-            }
-            memcpy(out_nodes + nb, node, len);
-            nb += len;
-            out_lens[nl++] = (uint32_t)len;
-            cnt++;
-            return 0;
-        };
-        int rc = proof_walk_emit(ctx, sroot, byhash, key, emit);
-        if (rc < 0)
+        if (pc.emit(t, sroot, slot_keys + 32ull * t, leaves, out_counts))
             return -1;
-        if ((rc == 0) != (pres[t] != 0)) {
-            set_err(ctx, "sre_storage_proof: internal presence mismatch");
-            return -1;
-        }
-        out_counts[t] = cnt;
     }
     return 0;
 }
@@ -5283,78 +4850,6 @@ extern "C" int sre_finish_top(sre_ctx *ctx, const uint8_t child_refs[16][33],
     return 0;
 }
 
-// same ordering as reth's TrieUpdates::into_sorted (updates.rs): account
-// rows first (path-sorted), then storage rows grouped by account key
-static bool row_less(const sre_update_row &a, const sre_update_row &b)
-{
-    if (a.kind != b.kind)
-        return a.kind < b.kind;
-    if (a.kind == 1) {
-        int c = memcmp(a.acct_key, b.acct_key, 32);
-        if (c)
-            return c < 0;
-    }
-    int minl = a.path_len < b.path_len ? a.path_len : b.path_len;
-    for (int k = 0; k < minl; ++k) {
-        uint8_t na_ = (a.path[k / 2] >> ((k & 1) ? 0 : 4)) & 0xf;
-        uint8_t nb_ = (b.path[k / 2] >> ((k & 1) ? 0 : 4)) & 0xf;
-        if (na_ != nb_)
-            return na_ < nb_;
-    }
-    return a.path_len < b.path_len;
-}
-
-// FNV-1a over a row's content (masks + hashes + root fields): the snapshot
-// compares rows by this to suppress unchanged re-emits from the net diff.
-static uint64_t row_h64(const sre_update_row &r)
-{
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](const void *p, size_t n) {
-        const uint8_t *b = (const uint8_t *)p;
-        for (size_t i = 0; i < n; ++i) {
-            h ^= b[i];
-            h *= 1099511628211ull;
-        }
-    };
-    mix(&r.state_mask, 2);
-    mix(&r.tree_mask, 2);
-    mix(&r.hash_mask, 2);
-    mix(&r.num_hashes, 1);
-    mix(&r.root_hash_set, 1);
-    mix(r.root_hash, 32);
-    mix(&r.hashes[0][0], 32ull * r.num_hashes);
-    return h;
-}
-
-static snap_row snap_of(const sre_update_row &r)
-{
-    snap_row s{};
-    s.kind = r.kind;
-    s.path_len = r.path_len;
-    memcpy(s.acct_key, r.acct_key, 32);
-    memcpy(s.path, r.path, 32);
-    s.h64 = row_h64(r);
-    return s;
-}
-
-// 3-way key compare, the same total order as row_less: paths are packed
-// high-nibble-first and zero-padded, so a 32-byte memcmp + length
-// tiebreak IS the nibble-lexicographic prefix-first order.
-static int snap_cmp(const snap_row &a, const snap_row &b)
-{
-    if (a.kind != b.kind)
-        return a.kind < b.kind ? -1 : 1;
-    if (a.kind == 1) {
-        int c = memcmp(a.acct_key, b.acct_key, 32);
-        if (c)
-            return c;
-    }
-    int c = memcmp(a.path, b.path, 32);
-    if (c)
-        return c;
-    return (int)a.path_len - (int)b.path_len;
-}
-
 // minimum resident ns for the closed-form small-delta storage merge;
 // SRE_ST_SMALL_MIN overrides (tests lower it to cover the path on small
 // states — the default keeps tiny states on the trivially-fast general
@@ -5462,23 +4957,11 @@ static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
         // validation of what k_ovl_delta_st_flags checked on device (the
         // owner lookup against the resident accounts rides in k_sds_marks).
         uint32_t bad = 0;
-        std::vector<std::array<uint8_t, 32>> dead;
-        for (uint64_t i = 0; i < n_acct; ++i)
-            if (acct_delta[i].deleted) {
-                std::array<uint8_t, 32> k;
-                memcpy(k.data(), acct_delta[i].key, 32);
-                dead.push_back(k);
-            }
+        std::vector<key32> dead = deleted_accounts(acct_delta, n_acct);
         for (uint64_t i = 0; i < n_st; ++i) {
             if (i && memcmp(&st_delta[i - 1], &st_delta[i], 64) >= 0)
                 bad |= 1u << E_UNSORTED_STORAGE; // or duplicate (acct,slot)
-            auto it = std::lower_bound(
-                dead.begin(), dead.end(), st_delta[i].acct_key,
-                [](const std::array<uint8_t, 32> &a, const uint8_t *b) {
-                    return memcmp(a.data(), b, 32) < 0;
-                });
-            if (it != dead.end() &&
-                memcmp(it->data(), st_delta[i].acct_key, 32) == 0)
+            if (key_in(dead, st_delta[i].acct_key))
                 bad |= 1u << E_ORPHAN_STORAGE; // row for a destroyed account
         }
         if (bad) {
@@ -5907,17 +5390,11 @@ static int incremental_root_impl(sre_ctx *ctx,
     // merged segments into a compact array and run the storage machinery
     // over it, scattering fresh roots over the carried ones
     if (n_st) {
-        std::vector<uint8_t> tkeys;
-        tkeys.reserve(32 * n_st);
-        for (uint64_t i = 0; i < n_st; ++i)
-            if (i == 0 || memcmp(st_delta[i].acct_key,
-                                 st_delta[i - 1].acct_key, 32) != 0)
-                tkeys.insert(tkeys.end(), st_delta[i].acct_key,
-                             st_delta[i].acct_key + 32);
-        uint32_t nt = (uint32_t)(tkeys.size() / 32);
+        std::vector<key32> tkeys = storage_delta_accounts(st_delta, n_st);
+        uint32_t nt = (uint32_t)tkeys.size();
         DBuf dtk(ctx), tlo(ctx), thi(ctx), taidx(ctx);
-        HIP_CHECK(ctx, dtk.alloc(tkeys.size()));
-        HIP_CHECK(ctx, hipMemcpyAsync(dtk.p, tkeys.data(), tkeys.size(),
+        HIP_CHECK(ctx, dtk.alloc(32ull * nt));
+        HIP_CHECK(ctx, hipMemcpyAsync(dtk.p, tkeys.data(), 32ull * nt,
                                       hipMemcpyHostToDevice, ctx->stream));
         HIP_CHECK(ctx, tlo.alloc((uint64_t)nt * 4));
         HIP_CHECK(ctx, thi.alloc((uint64_t)nt * 4));
@@ -6126,20 +5603,8 @@ extern "C" int sre_incremental_root_with_updates(
         return -1;
     }
     // region keys from the (sorted) delta, host side
-    std::vector<std::array<uint8_t, 32>> touched, destroyed;
-    for (uint64_t i = 0; i < n_st; ++i)
-        if (i == 0 ||
-            memcmp(st_delta[i].acct_key, st_delta[i - 1].acct_key, 32)) {
-            std::array<uint8_t, 32> k;
-            memcpy(k.data(), st_delta[i].acct_key, 32);
-            touched.push_back(k);
-        }
-    for (uint64_t i = 0; i < n_acct; ++i)
-        if (acct_delta[i].deleted) {
-            std::array<uint8_t, 32> k;
-            memcpy(k.data(), acct_delta[i].key, 32);
-            destroyed.push_back(k);
-        }
+    std::vector<key32> touched = storage_delta_accounts(st_delta, n_st);
+    std::vector<key32> destroyed = deleted_accounts(acct_delta, n_acct);
 
     ctx->retain_updates = true;
     ctx->updates.clear();
@@ -6157,96 +5622,10 @@ extern "C" int sre_incremental_root_with_updates(
         return rc;
     }
 
-    // NET diff: emitted rows vs the retained snapshot. The engine
-    // re-emits every row in the rebuilt region (depth <= 4 account rows,
-    // dirty/uncovered cells, rebuilt storage tries); unchanged re-emits
-    // are suppressed by content hash, region rows missing from the
-    // emission become removals (walker.rs:363-369 semantics), destroyed
-    // accounts get whole-trie markers (updates.rs:154-157).
-    std::vector<sre_update_row> E;
-    E.swap(ctx->updates);
-    std::sort(E.begin(), E.end(), row_less);
-    std::vector<snap_row> Es;
-    Es.reserve(E.size());
-    for (auto &r : E) {
-        r.removed = 0;
-        Es.push_back(snap_of(r));
-    }
-
-    auto key_in = [](const std::vector<std::array<uint8_t, 32>> &v,
-                     const uint8_t *k) {
-        auto it = std::lower_bound(
-            v.begin(), v.end(), k,
-            [](const std::array<uint8_t, 32> &a, const uint8_t *b) {
-                return memcmp(a.data(), b, 32) < 0;
-            });
-        return it != v.end() && memcmp(it->data(), k, 32) == 0;
-    };
-    auto in_region = [&](const snap_row &s) {
-        if (s.kind == 0) {
-            if (s.path_len <= 4)
-                return true;
-            // empty bitmap: the delta emptied the state (the impl returns
-            // before the account pass) — everything is rebuilt region
-            if (bitmap.empty())
-                return true;
-            uint32_t cell = ((uint32_t)s.path[0] << 12) |
-                            ((uint32_t)s.path[1] << 4) |
-                            ((uint32_t)s.path[2] >> 4);
-            return bitmap[cell] != 0;
-        }
-        return key_in(touched, s.acct_key);
-    };
-
     std::vector<sre_update_row> diff;
     std::vector<snap_row> nsnap;
-    nsnap.reserve(ctx->snap.size() + Es.size());
-    size_t i = 0, j = 0;
-    while (i < ctx->snap.size() || j < Es.size()) {
-        int c;
-        if (i >= ctx->snap.size())
-            c = 1;
-        else if (j >= Es.size())
-            c = -1;
-        else
-            c = snap_cmp(ctx->snap[i], Es[j]);
-        if (c == 0) {
-            if (ctx->snap[i].h64 != Es[j].h64)
-                diff.push_back(E[j]); // changed row
-            nsnap.push_back(Es[j]);
-            i++;
-            j++;
-        } else if (c > 0) { // new row
-            diff.push_back(E[j]);
-            nsnap.push_back(Es[j]);
-            j++;
-        } else { // snapshot row not re-emitted this pass
-            const snap_row &s = ctx->snap[i];
-            if (s.kind == 1 && key_in(destroyed, s.acct_key)) {
-                // dropped wholesale; the removed=2 marker covers the trie
-            } else if (in_region(s)) {
-                sre_update_row rr{};
-                rr.kind = s.kind;
-                rr.path_len = s.path_len;
-                memcpy(rr.path, s.path, 32);
-                if (s.kind == 1)
-                    memcpy(rr.acct_key, s.acct_key, 32);
-                rr.removed = 1;
-                diff.push_back(rr);
-            } else {
-                nsnap.push_back(s); // untouched region: row kept
-            }
-            i++;
-        }
-    }
-    for (const auto &k : destroyed) { // StorageTrieUpdates::set_deleted(true)
-        sre_update_row rr{};
-        rr.kind = 1;
-        memcpy(rr.acct_key, k.data(), 32);
-        rr.removed = 2;
-        diff.push_back(rr);
-    }
-    std::sort(diff.begin(), diff.end(), row_less);
+    updates_net_diff(ctx->snap, std::move(ctx->updates), bitmap, touched,
+                     destroyed, diff, nsnap);
     ctx->snap.swap(nsnap);
     ctx->updates.swap(diff);
     ctx->snap_valid = true;
@@ -6301,12 +5680,8 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
                  const std::array<uint8_t, 64> &b) {
                   return memcmp(a.data(), b.data(), 32) < 0;
               });
-    std::vector<uint8_t> tkeys; // touched storage accounts (delta, sorted)
-    for (uint64_t i = 0; i < n_st; ++i)
-        if (i == 0 ||
-            memcmp(st_delta[i].acct_key, st_delta[i - 1].acct_key, 32))
-            tkeys.insert(tkeys.end(), st_delta[i].acct_key,
-                         st_delta[i].acct_key + 32);
+    // touched storage accounts (delta, sorted)
+    std::vector<key32> tkeys = storage_delta_accounts(st_delta, n_st);
 
     if (apply_delta_impl(ctx, acct_delta, n_acct, st_delta, n_st, nullptr))
         return -1;
@@ -6340,14 +5715,14 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
         if (!kv.empty())
             HIP_CHECK(ctx, hipMemcpyAsync(dkv.p, kv.data(), kv.size() * 64,
                                           hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK(ctx, dtk.alloc(tkeys.empty() ? 32 : tkeys.size()));
+        HIP_CHECK(ctx, dtk.alloc(tkeys.empty() ? 32 : tkeys.size() * 32));
         if (!tkeys.empty())
-            HIP_CHECK(ctx, hipMemcpyAsync(dtk.p, tkeys.data(), tkeys.size(),
+            HIP_CHECK(ctx, hipMemcpyAsync(dtk.p, tkeys.data(), tkeys.size() * 32,
                                           hipMemcpyHostToDevice, ctx->stream));
         LAUNCH(ctx, k_seg_need, grid_for(n_seg), BLOCK, ctx->stream, ctx->d_st,
                sg.seg_start.as<uint32_t>(), n_seg, dkv.as<uint8_t>(),
                (uint64_t)kv.size(), dtk.as<uint8_t>(),
-               (uint64_t)(tkeys.size() / 32), sg.seg_acct.as<uint32_t>(),
+               (uint64_t)tkeys.size(), sg.seg_acct.as<uint32_t>(),
                acct_roots.as<uint8_t>(), need.as<uint32_t>());
         std::vector<uint32_t> need_h(n_seg), start_h(n_seg);
         HIP_CHECK(ctx, hipMemcpy(need_h.data(), need.p, 4ull * n_seg,

@@ -378,28 +378,8 @@ class StateRootEngine:
         targets: list of 32-byte hashed keys. cap_nodes / cap_lens
         override the output capacities (bytes / entries) handed to the
         engine; the defaults hold any proof."""
-        n = len(targets)
-        tarr = np.frombuffer(b"".join(targets), dtype=np.uint8).reshape(n, 32)
-        tarr = np.ascontiguousarray(tarr)
-        if cap_nodes is None:
-            cap_nodes = n * 130 * 560 + 4096
-        if cap_lens is None:
-            cap_lens = n * 132
-        nodes = np.zeros(cap_nodes, dtype=np.uint8)
-        lens = np.zeros(cap_lens, dtype=np.uint32)
-        counts = np.zeros(n, dtype=np.uint32)
-        self._check(self._lib.sre_account_proof(
-            ctypes.c_void_p(self._ctx), _np_ptr(tarr), ctypes.c_uint64(n),
-            _np_ptr(nodes), ctypes.c_uint64(cap_nodes),
-            _np_ptr(lens), ctypes.c_uint64(cap_lens), _np_ptr(counts)))
-        out, off, li = [], 0, 0
-        for t in range(n):
-            tl = []
-            for _ in range(int(counts[t])):
-                ln = int(lens[li]); li += 1
-                tl.append(nodes[off:off + ln].tobytes()); off += ln
-            out.append(tl)
-        return out
+        return self._proofs(self._lib.sre_account_proof, [targets],
+                            cap_nodes, cap_lens)
 
     def storage_proof(self, acct_keys, slot_keys, cap_nodes=None,
                       cap_lens=None):
@@ -409,33 +389,42 @@ class StateRootEngine:
         Returns (roots, proofs) — per target the account's storage root
         and the root-first node-RLP list of its storage trie. cap_nodes /
         cap_lens as in account_proof."""
-        n = len(acct_keys)
-        assert len(slot_keys) == n
-        aarr = np.ascontiguousarray(
-            np.frombuffer(b"".join(acct_keys), dtype=np.uint8).reshape(n, 32))
-        sarr = np.ascontiguousarray(
-            np.frombuffer(b"".join(slot_keys), dtype=np.uint8).reshape(n, 32))
+        assert len(slot_keys) == len(acct_keys)
+        roots = np.zeros((len(acct_keys), 32), dtype=np.uint8)
+        proofs = self._proofs(self._lib.sre_storage_proof,
+                              [acct_keys, slot_keys], cap_nodes, cap_lens,
+                              [roots])
+        return [bytes(r) for r in roots], proofs
+
+    def _proofs(self, fn, key_lists, cap_nodes, cap_lens, extra_out=()):
+        """Call a proof entry point (include/sre.h): its 32-byte key lists,
+        the target count, extra_out, then the node / length / count
+        outputs: counts[t] nodes per target, their byte lengths in lens,
+        their bytes back to back in nodes. Returns per-target node lists."""
+        n = len(key_lists[0])
+        keys = [np.ascontiguousarray(np.frombuffer(
+            b"".join(k), dtype=np.uint8).reshape(n, 32)) for k in key_lists]
         if cap_nodes is None:
             cap_nodes = n * 130 * 560 + 4096
         if cap_lens is None:
             cap_lens = n * 132
-        roots = np.zeros((n, 32), dtype=np.uint8)
         nodes = np.zeros(cap_nodes, dtype=np.uint8)
         lens = np.zeros(cap_lens, dtype=np.uint32)
         counts = np.zeros(n, dtype=np.uint32)
-        self._check(self._lib.sre_storage_proof(
-            ctypes.c_void_p(self._ctx), _np_ptr(aarr), _np_ptr(sarr),
-            ctypes.c_uint64(n), _np_ptr(roots),
+        self._check(fn(
+            ctypes.c_void_p(self._ctx), *[_np_ptr(k) for k in keys],
+            ctypes.c_uint64(n), *[_np_ptr(o) for o in extra_out],
             _np_ptr(nodes), ctypes.c_uint64(cap_nodes),
             _np_ptr(lens), ctypes.c_uint64(cap_lens), _np_ptr(counts)))
         out, off, li = [], 0, 0
-        for t in range(n):
+        for cnt in counts:
             tl = []
-            for _ in range(int(counts[t])):
-                ln = int(lens[li]); li += 1
-                tl.append(nodes[off:off + ln].tobytes()); off += ln
+            for ln in lens[li:li + int(cnt)]:
+                tl.append(nodes[off:off + int(ln)].tobytes())
+                off += int(ln)
+            li += int(cnt)
             out.append(tl)
-        return [bytes(r) for r in roots], out
+        return out
 
     def storage_roots(self, n) -> np.ndarray:
         out = np.empty((n, 32), dtype=np.uint8)
