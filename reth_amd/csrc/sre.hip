@@ -49,22 +49,12 @@
 
 #include "../../include/sre.h"
 #include "junction.h"
+#include "merge_plan.h" // the E_* bit numbers live there
 #include "proof_host.h"
 #include "radix.h"
 #include "updates_diff.h"
 
 #define BLOCK 256u
-
-enum {
-    E_OK = 0,
-    E_UNSORTED_ACCT = 1,
-    E_UNSORTED_STORAGE = 2,
-    E_ORPHAN_STORAGE = 3,
-    E_ZERO_VALUE = 4,
-    E_INTERNAL = 5,
-    E_DUP_ADDRESS = 6,
-    E_DUP_STORAGE = 7,
-};
 
 // ---------------------------------------------------------------------------
 // device keccak-256 (one sponge per lane, state in registers)
@@ -2518,7 +2508,7 @@ __global__ void k_sd_scatter(const sre_account_entry *__restrict__ base,
             p < nd &&
             cmp_key32(dl[p].key, base[i0 + blockDim.x - 1].key) == 0;
         if (!lastmatch) {
-            uint64_t j0 = i0 - m_excl[p] + eff_excl[p];
+            uint64_t j0 = merged_pos(i0, m_excl[p], eff_excl[p]);
             const uint64_t *s8 = (const uint64_t *)&base[i0];
             uint64_t *d8 = (uint64_t *)&out[j0];
             // static trip count: issue all 13 loads before any store
@@ -2529,14 +2519,14 @@ __global__ void k_sd_scatter(const sre_account_entry *__restrict__ base,
 #pragma unroll
             for (int w = 0; w < 13; ++w)
                 d8[threadIdx.x + (uint32_t)w * BLOCK] = v[w];
-            map[i] = (uint32_t)(i - m_excl[p] + eff_excl[p]);
+            map[i] = (uint32_t)merged_pos(i, m_excl[p], eff_excl[p]);
             return;
         }
     }
     if (i > nb)
         return;
     if (i == nb) {
-        map[nb] = (uint32_t)(nb - m_excl[nd] + eff_excl[nd]);
+        map[nb] = (uint32_t)merged_pos(nb, m_excl[nd], eff_excl[nd]);
         return;
     }
     uint64_t lo = plo_s, hi = phi_s;
@@ -2551,7 +2541,7 @@ __global__ void k_sd_scatter(const sre_account_entry *__restrict__ base,
     }
     uint64_t p = lo;
     bool m = p < nd && cmp_key32(dl[p].key, base[i].key) == 0;
-    uint32_t j = (uint32_t)(i - m_excl[p] + eff_excl[p]);
+    uint32_t j = (uint32_t)merged_pos(i, m_excl[p], eff_excl[p]);
     map[i] = j;
     if (!m) {
         // 13 u64 copies (entries are 8-B aligned at the 104-B stride)
@@ -2577,7 +2567,7 @@ __global__ void k_sd_place(const sre_account_delta *__restrict__ dl,
     uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nd)
         return;
-    uint32_t j = (uint32_t)(bpos[k] - m_excl[k] + eff_excl[k]);
+    uint32_t j = (uint32_t)merged_pos(bpos[k], m_excl[k], eff_excl[k]);
     newpos[k] = j;
     if (!dl[k].deleted) {
         sre_account_entry e;
@@ -2635,12 +2625,6 @@ __global__ void k_sd_lcp_patch(const sre_account_entry *__restrict__ out,
 // most a few thousand ranges, all L1/L2-resident. Replaces the O(ns)
 // flags + scans + posmap of the general storage merge; what remains is
 // the irreducible array rewrite.
-
-// k_sds_marks' per-row word, read back by the host
-enum : uint32_t {
-    SDS_MATCH = 1,  // (acct, slot) is resident: the row replaces/deletes it
-    SDS_ORPHAN = 2, // nonzero row whose account is neither resident nor upserted
-};
 
 __global__ void k_sds_marks(const sre_storage_entry *__restrict__ base,
                             uint64_t ns,
@@ -2701,30 +2685,7 @@ __global__ void k_sds_wipes(const sre_storage_entry *__restrict__ base,
     whi[a] = (uint32_t)lo2;
 }
 
-__device__ __forceinline__ uint64_t wipes_before(const uint32_t *wlo,
-                                                 const uint32_t *whi,
-                                                 const uint32_t *wsum,
-                                                 uint32_t ndel, uint64_t i,
-                                                 bool *wiped)
-{
-    // last range with wlo <= i
-    int lo = 0, hi = (int)ndel;
-    while (lo < hi) {
-        int mid = (lo + hi) / 2;
-        if ((uint64_t)wlo[mid] <= i)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    int r = lo - 1;
-    *wiped = false;
-    if (r < 0)
-        return 0;
-    uint32_t clip = i < whi[r] ? (uint32_t)i : whi[r];
-    *wiped = i < whi[r];
-    return wsum[r] + (clip > wlo[r] ? clip - wlo[r] : 0);
-}
-
+// wipes_before / merged_pos: merge_plan.h
 __global__ void k_sds_scatter(const sre_storage_entry *__restrict__ base,
                               uint64_t ns,
                               const sre_storage_entry *__restrict__ dl,
@@ -2766,7 +2727,7 @@ __global__ void k_sds_scatter(const sre_storage_entry *__restrict__ base,
                          cmp_key64((const uint8_t *)&dl[p],
                                    (const uint8_t *)&base[last]) == 0;
         if (!lastmatch && !w0 && !w1 && wb0 == wb1) {
-            uint64_t j0 = i0 - m_excl[p] - wb0 + eff_excl[p];
+            uint64_t j0 = merged_pos(i0, m_excl[p], eff_excl[p], wb0);
             const uint64_t *s8 = (const uint64_t *)&base[i0];
             uint64_t *d8 = (uint64_t *)&out[j0];
             uint64_t v[12];
@@ -2797,7 +2758,7 @@ __global__ void k_sds_scatter(const sre_storage_entry *__restrict__ base,
                                         (const uint8_t *)&base[i]) == 0;
     if (matched || wiped)
         return;
-    uint64_t j = i - m_excl[p] - wb + eff_excl[p];
+    uint64_t j = merged_pos(i, m_excl[p], eff_excl[p], wb);
     const uint64_t *s8 = (const uint64_t *)&base[i];
     uint64_t *d8 = (uint64_t *)&out[j];
 #pragma unroll
@@ -2827,7 +2788,7 @@ __global__ void k_sds_place(const sre_storage_entry *__restrict__ dl,
         return;
     bool wiped;
     uint64_t wb = wipes_before(wlo, whi, wsum, ndel, bpos[k], &wiped);
-    uint64_t j = bpos[k] - m_excl[k] - wb + eff_excl[k];
+    uint64_t j = merged_pos(bpos[k], m_excl[k], eff_excl[k], wb);
     const uint64_t *s8 = (const uint64_t *)&dl[k];
     uint64_t *d8 = (uint64_t *)&out[j];
 #pragma unroll
@@ -3189,21 +3150,39 @@ __global__ void k_scan_add(uint32_t *__restrict__ out, uint64_t n,
         HIP_CHECK(ctx, hipGetLastError());                                       \
     } while (0)
 
+struct sre_ctx;
+struct DBuf;
+
+// One resident input array (accounts or storage): borrowed from the caller,
+// or owned and then either hipMalloc'd (upload) or a pool buffer (adopt).
+template <typename T> struct resident {
+    const T *d = nullptr;
+    uint64_t n = 0;
+    bool own = false;
+    // nonzero when the owned array came from the pool (a delta merge
+    // replaces the state every call; pooling avoids a 21 GB hipMalloc+Free
+    // per delta at the 200M-account config)
+    size_t pool_bytes = 0;
+    void release(sre_ctx *ctx);
+    void adopt(sre_ctx *ctx, DBuf &buf, uint64_t count);
+    int borrow(sre_ctx *ctx, const void *d_entries, uint64_t count);
+    int upload(sre_ctx *ctx, const T *entries, uint64_t count);
+};
+
+// A retained (non-pool) device buffer and its capacity in elements.
+struct retained_buf {
+    void *p = nullptr;
+    uint64_t cap = 0;
+    int grow(sre_ctx *ctx, uint64_t want, uint64_t elem_bytes = 1);
+};
+
 struct sre_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr; // branch-assemble pipeline stage
     std::string err;
-    const sre_account_entry *d_acct = nullptr;
-    uint64_t na = 0;
-    bool own_acct = false;
-    const sre_storage_entry *d_st = nullptr;
-    uint64_t ns = 0;
-    bool own_st = false;
-    // nonzero when the owned input array came from the pool (apply_delta
-    // replaces the state every call; pooling avoids a 21 GB hipMalloc+Free
-    // per delta at the 200M-account config)
-    size_t acct_pool_bytes = 0, st_pool_bytes = 0;
+    resident<sre_account_entry> acct;
+    resident<sre_storage_entry> st;
     sre_stats stats{};
     // branch-pipeline path counters (sre_get_path_counters): [0] levels that
     // used the class partition, [1] groups sent to k_branch_fused1,
@@ -3234,19 +3213,14 @@ struct sre_ctx {
     // at depths < CELL_NIBBLES during a full account pass.
     bool retain_cells = false;   // capture on the next root computation
     bool cells_valid = false;    // retained rows match the resident state
-    void *d_cap_rows = nullptr;  // cap_row[cap_count]
-    uint64_t cap_count = 0, cap_capacity = 0;
-    void *d_roots_ret = nullptr; // retained per-account storage roots (na x 32)
-    uint64_t roots_ret_capacity = 0; // in accounts
-    void *d_roots_ret2 = nullptr; // ping-pong partner (incremental updates)
-    uint64_t roots_ret2_capacity = 0;
+    retained_buf cap_rows;       // cap_row[cap_count]
+    uint64_t cap_count = 0;
+    retained_buf roots_ret;  // retained per-account storage roots (na x 32)
+    retained_buf roots_ret2; // ping-pong partner (incremental updates)
     // retained account-lcp (na+1 i8) for small-delta repair: chained
     // deltas patch O(delta) boundary lcps instead of recomputing all na
-    void *d_lcp_ret = nullptr;
-    uint64_t lcp_ret_capacity = 0; // bytes
-    void *d_lcp_ret2 = nullptr;
-    uint64_t lcp_ret2_capacity = 0;
-    bool lcp_valid = false; // d_lcp_ret matches the resident accounts
+    retained_buf lcp_ret, lcp_ret2;
+    bool lcp_valid = false; // lcp_ret matches the resident accounts
     // size-class buffer pool: the level machinery allocates/frees dozens of
     // transient arrays per level; hipMalloc latency would dominate small
     // jobs. Freed buffers are cached by power-of-2 class and reused (also
@@ -3308,30 +3282,6 @@ static void pool_put(sre_ctx *ctx, size_t bytes, void *p)
         ctx->pool.emplace_back(pool_class(bytes), p);
 }
 
-static void release_acct(sre_ctx *ctx)
-{
-    if (ctx->own_acct && ctx->d_acct) {
-        if (ctx->acct_pool_bytes)
-            pool_put(ctx, ctx->acct_pool_bytes, (void *)ctx->d_acct);
-        else
-            (void)hipFree((void *)ctx->d_acct);
-    }
-    ctx->d_acct = nullptr;
-    ctx->acct_pool_bytes = 0;
-}
-
-static void release_st(sre_ctx *ctx)
-{
-    if (ctx->own_st && ctx->d_st) {
-        if (ctx->st_pool_bytes)
-            pool_put(ctx, ctx->st_pool_bytes, (void *)ctx->d_st);
-        else
-            (void)hipFree((void *)ctx->d_st);
-    }
-    ctx->d_st = nullptr;
-    ctx->st_pool_bytes = 0;
-}
-
 static std::string g_err;
 
 static void set_err(sre_ctx *ctx, const std::string &msg)
@@ -3375,18 +3325,12 @@ extern "C" void sre_destroy(sre_ctx *ctx)
 {
     if (!ctx)
         return;
-    release_acct(ctx);
-    release_st(ctx);
-    if (ctx->d_cap_rows)
-        (void)hipFree(ctx->d_cap_rows);
-    if (ctx->d_roots_ret)
-        (void)hipFree(ctx->d_roots_ret);
-    if (ctx->d_roots_ret2)
-        (void)hipFree(ctx->d_roots_ret2);
-    if (ctx->d_lcp_ret)
-        (void)hipFree(ctx->d_lcp_ret);
-    if (ctx->d_lcp_ret2)
-        (void)hipFree(ctx->d_lcp_ret2);
+    ctx->acct.release(ctx);
+    ctx->st.release(ctx);
+    for (retained_buf *b : {&ctx->cap_rows, &ctx->roots_ret, &ctx->roots_ret2,
+                            &ctx->lcp_ret, &ctx->lcp_ret2})
+        if (b->p)
+            (void)hipFree(b->p);
     for (auto &e : ctx->pool)
         (void)hipFree(e.second);
     ctx->pool.clear();
@@ -3401,7 +3345,7 @@ extern "C" void sre_destroy(sre_ctx *ctx)
 // capacity contract)
 static int check_cap(sre_ctx *ctx, uint64_t n)
 {
-    if (n >= 0xFFFFFFFFull) {
+    if (!count_fits(n)) {
         set_err(ctx, "entry count exceeds the 2^32-1 per-GPU limit "
                      "(u32 leaf intervals); shard across GPUs");
         return -1;
@@ -3430,68 +3374,60 @@ static int begin_call(sre_ctx *ctx, bool zero_stats)
     return 0;
 }
 
-// Replace one resident input array (accounts or storage; `release` frees
-// the previous one) with an engine-owned copy of host entries.
+// Replace the array with an engine-owned copy of host entries.
 template <typename T>
-static int upload_entries(sre_ctx *ctx, void (*release)(sre_ctx *), const T **d,
-                          uint64_t *count, bool *own, const T *entries, uint64_t n)
+int resident<T>::upload(sre_ctx *ctx, const T *entries, uint64_t count)
 {
-    if (check_cap(ctx, n))
+    if (check_cap(ctx, count))
         return -1;
     invalidate_retention(ctx);
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
     release(ctx);
     void *p = nullptr;
-    if (n) {
-        HIP_CHECK(ctx, hipMalloc(&p, n * sizeof(T)));
-        HIP_CHECK(ctx, hipMemcpy(p, entries, n * sizeof(T), hipMemcpyHostToDevice));
+    if (count) {
+        HIP_CHECK(ctx, hipMalloc(&p, count * sizeof(T)));
+        HIP_CHECK(ctx, hipMemcpy(p, entries, count * sizeof(T), hipMemcpyHostToDevice));
     }
-    *d = (const T *)p;
-    *count = n;
-    *own = true;
+    d = (const T *)p;
+    n = count;
+    own = true;
     return 0;
 }
 
 // Borrow device-resident inputs (zero-copy; caller keeps them alive).
 template <typename T>
-static int borrow_entries(sre_ctx *ctx, void (*release)(sre_ctx *), const T **d,
-                          uint64_t *count, bool *own, const void *d_entries,
-                          uint64_t n)
+int resident<T>::borrow(sre_ctx *ctx, const void *d_entries, uint64_t count)
 {
-    if (check_cap(ctx, n))
+    if (check_cap(ctx, count))
         return -1;
     invalidate_retention(ctx);
     release(ctx);
-    *d = (const T *)d_entries;
-    *count = n;
-    *own = false;
+    d = (const T *)d_entries;
+    n = count;
+    own = false;
     return 0;
 }
 
 extern "C" int sre_upload_accounts(sre_ctx *ctx, const sre_account_entry *entries,
                                    uint64_t n)
 {
-    return upload_entries(ctx, release_acct, &ctx->d_acct, &ctx->na,
-                          &ctx->own_acct, entries, n);
+    return ctx->acct.upload(ctx, entries, n);
 }
 
 extern "C" int sre_upload_storage(sre_ctx *ctx, const sre_storage_entry *entries,
                                   uint64_t n)
 {
-    return upload_entries(ctx, release_st, &ctx->d_st, &ctx->ns, &ctx->own_st,
-                          entries, n);
+    return ctx->st.upload(ctx, entries, n);
 }
 
 extern "C" int sre_set_accounts_device(sre_ctx *ctx, const void *d_entries, uint64_t n)
 {
-    return borrow_entries(ctx, release_acct, &ctx->d_acct, &ctx->na,
-                          &ctx->own_acct, d_entries, n);
+    return ctx->acct.borrow(ctx, d_entries, n);
 }
 
 extern "C" int sre_set_storage_device(sre_ctx *ctx, const void *d_entries, uint64_t n)
 {
-    return borrow_entries(ctx, release_st, &ctx->d_st, &ctx->ns, &ctx->own_st,
-                          d_entries, n);
+    return ctx->st.borrow(ctx, d_entries, n);
 }
 
 extern "C" int sre_keccak_batch_device(sre_ctx *ctx, const void *d_in, uint64_t stride,
@@ -3558,8 +3494,44 @@ struct DBuf {
         }
         return hipMalloc(&p, sz);
     }
+    // hand the buffer out (sz stays: its size class); the DBuf is empty after
+    void *take()
+    {
+        void *q = p;
+        p = nullptr;
+        return q;
+    }
     template <typename T> T *as() { return (T *)p; }
 };
+
+// Free or return to the pool whatever the engine owns; n and own stay until
+// the caller installs the next array.
+template <typename T> void resident<T>::release(sre_ctx *ctx)
+{
+    if (own && d) {
+        if (pool_bytes) {
+            DBuf back(ctx); // its destructor returns the buffer to the pool
+            back.p = (void *)d;
+            back.sz = pool_bytes;
+        } else {
+            (void)hipFree((void *)d);
+        }
+    }
+    d = nullptr;
+    pool_bytes = 0;
+}
+
+// Install a merged or sorted array built in a pool buffer (reused across
+// repeated deltas). Until this runs the DBuf owns it, so a failed build
+// returns the buffer on whatever path it leaves by.
+template <typename T> void resident<T>::adopt(sre_ctx *ctx, DBuf &buf, uint64_t count)
+{
+    release(ctx);
+    pool_bytes = buf.sz;
+    d = (const T *)buf.take();
+    n = count;
+    own = true;
+}
 
 // Owning HIP event. A failed create leaves a null event, which the first
 // checked record/wait on it reports.
@@ -3600,25 +3572,47 @@ static int alloc_err_flag(sre_ctx *ctx, DBuf &err)
     return 0;
 }
 
-// Grow a retained (non-pool) device buffer to `want` elements; contents
-// are not preserved. The bigger buffer is allocated, and the stream
-// drained, before the old one is freed: queued work may still read it.
-static int grow_retained(sre_ctx *ctx, void **slot, uint64_t *capacity,
-                         uint64_t want, uint64_t elem_bytes = 1)
+// Grow to `want` elements; contents are not preserved. The bigger buffer
+// is allocated, and the stream drained, before the old one is freed:
+// queued work may still read it.
+int retained_buf::grow(sre_ctx *ctx, uint64_t want, uint64_t elem_bytes)
 {
-    if (*capacity >= want)
+    if (cap >= want)
         return 0;
     void *bigger = nullptr;
     HIP_CHECK(ctx, hipMalloc(&bigger, want * elem_bytes));
-    if (*slot) {
+    if (p) {
         hipError_t e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess)
             (void)hipFree(bigger);
         HIP_CHECK(ctx, e);
-        (void)hipFree(*slot);
+        (void)hipFree(p);
     }
-    *slot = bigger;
-    *capacity = want;
+    p = bigger;
+    cap = want;
+    return 0;
+}
+
+// Allocate b for n elements and queue their upload on ctx->stream; n == 0
+// allocates the minimum and copies nothing.
+template <typename T>
+static int to_device(sre_ctx *ctx, DBuf &b, const T *src, uint64_t n)
+{
+    HIP_CHECK(ctx, b.alloc(n * sizeof(T)));
+    if (n)
+        HIP_CHECK(ctx, hipMemcpyAsync(b.p, src, n * sizeof(T),
+                                      hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+
+// Blocking read-back of b's first n elements.
+template <typename T>
+static int to_host(sre_ctx *ctx, std::vector<T> &dst, const DBuf &b, uint64_t n)
+{
+    dst.resize(n);
+    if (n)
+        HIP_CHECK(ctx, hipMemcpy(dst.data(), b.p, n * sizeof(T),
+                                 hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -4098,7 +4092,7 @@ static int segment_ids(sre_ctx *ctx, const sre_storage_entry *d_st, uint64_t ns,
            sg.seg_start.as<uint32_t>(), sg.lcp.as<int8_t>(), recs,
            seg_roots ? seg_roots->as<uint8_t>() : nullptr);
     LAUNCH(ctx, k_seg_acct, grid_for(sg.n_seg), BLOCK, ctx->stream, d_st,
-           sg.seg_start.as<uint32_t>(), sg.n_seg, ctx->d_acct, ctx->na,
+           sg.seg_start.as<uint32_t>(), sg.n_seg, ctx->acct.d, ctx->acct.n,
            sg.seg_acct.as<uint32_t>(), d_err);
     return 0;
 }
@@ -4138,8 +4132,8 @@ static int run_storage_pass(sre_ctx *ctx, uint8_t *d_acct_roots, pass_out *po,
                             const storage_subset &sub = {})
 {
     const bool subset = sub.entries != nullptr;
-    uint64_t ns = subset ? sub.n : ctx->ns, na = ctx->na;
-    const sre_storage_entry *d_st = subset ? sub.entries : ctx->d_st;
+    uint64_t ns = subset ? sub.n : ctx->st.n, na = ctx->acct.n;
+    const sre_storage_entry *d_st = subset ? sub.entries : ctx->st.d;
     if (!subset)
         LAUNCH(ctx, k_fill_empty_roots, grid_for(na), BLOCK, ctx->stream,
                d_acct_roots, na);
@@ -4204,9 +4198,9 @@ static int run_storage_pass(sre_ctx *ctx, uint8_t *d_acct_roots, pass_out *po,
     if (ctx->retain_updates && ctx->updates.size() > upd_start) {
         // patch acct_key from the stashed seg ids: seg -> account index ->
         // 32-byte hashed key
-        std::vector<uint32_t> seg_acct_h(n_seg);
-        HIP_CHECK(ctx, hipMemcpy(seg_acct_h.data(), sg.seg_acct.p,
-                                 (uint64_t)n_seg * 4, hipMemcpyDeviceToHost));
+        std::vector<uint32_t> seg_acct_h;
+        if (to_host(ctx, seg_acct_h, sg.seg_acct, n_seg))
+            return -1;
         std::vector<uint8_t> keys_h;
         // sparse incremental subset: fetch only the touched accounts' keys
         // instead of all na x 32 B
@@ -4214,14 +4208,14 @@ static int run_storage_pass(sre_ctx *ctx, uint8_t *d_acct_roots, pass_out *po,
         if (!sparse) {
             // full pass (or dense subset): strided D2H of the key column
             keys_h.resize((uint64_t)na * 32);
-            HIP_CHECK(ctx, hipMemcpy2D(keys_h.data(), 32, ctx->d_acct,
+            HIP_CHECK(ctx, hipMemcpy2D(keys_h.data(), 32, ctx->acct.d,
                                        sizeof(sre_account_entry), 32, na,
                                        hipMemcpyDeviceToHost));
         } else {
             keys_h.resize((uint64_t)n_seg * 32);
             for (uint32_t s2 = 0; s2 < n_seg; ++s2)
                 HIP_CHECK(ctx, hipMemcpy(keys_h.data() + 32ull * s2,
-                                         (const uint8_t *)&ctx->d_acct
+                                         (const uint8_t *)&ctx->acct.d
                                              [seg_acct_h[s2]],
                                          32, hipMemcpyDeviceToHost));
         }
@@ -4256,11 +4250,10 @@ static int run_storage_intervals(sre_ctx *ctx, const uint32_t *d_lo,
     uint32_t n_iv = (uint32_t)offs_host.size() - 1;
     uint64_t total = offs_host[n_iv];
     DBuf doffs(ctx), compact(ctx);
-    HIP_CHECK(ctx, doffs.alloc(4ull * (n_iv + 1)));
-    HIP_CHECK(ctx, hipMemcpyAsync(doffs.p, offs_host.data(), 4ull * (n_iv + 1),
-                                  hipMemcpyHostToDevice, ctx->stream));
+    if (to_device(ctx, doffs, offs_host.data(), (uint64_t)n_iv + 1))
+        return -1;
     HIP_CHECK(ctx, compact.alloc(total * sizeof(sre_storage_entry)));
-    LAUNCH(ctx, k_gather_touched, grid_for(total), BLOCK, ctx->stream, ctx->d_st,
+    LAUNCH(ctx, k_gather_touched, grid_for(total), BLOCK, ctx->stream, ctx->st.d,
            d_lo, d_hi, doffs.as<uint32_t>(), n_iv, total,
            compact.as<sre_storage_entry>());
     return run_storage_pass(ctx, d_acct_roots, po, d_err, proof_capture{},
@@ -4273,7 +4266,7 @@ static int run_account_pass(sre_ctx *ctx, const uint8_t *d_storage_roots, int su
                             const cell_capture &cap = {},
                             const proof_capture &proof = {})
 {
-    uint64_t na = ctx->na;
+    uint64_t na = ctx->acct.n;
     DBuf lcp(ctx), recs(ctx), depths(ctx), hist(ctx);
     HIP_CHECK(ctx, lcp.alloc(na + 1));
     HIP_CHECK(ctx, recs.alloc(na * sizeof(node_rec)));
@@ -4281,7 +4274,7 @@ static int run_account_pass(sre_ctx *ctx, const uint8_t *d_storage_roots, int su
     HIP_CHECK(ctx, hist.alloc(66 * 4));
     HIP_CHECK(ctx, hipMemsetAsync(hist.p, 0, 66 * 4, ctx->stream));
 
-    LAUNCH(ctx, k_lcp_account, grid_for(na + 1), BLOCK, ctx->stream, ctx->d_acct,
+    LAUNCH(ctx, k_lcp_account, grid_for(na + 1), BLOCK, ctx->stream, ctx->acct.d,
            na, subtree, lcp.as<int8_t>(), d_err);
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (check_err(ctx, d_err))
@@ -4289,7 +4282,7 @@ static int run_account_pass(sre_ctx *ctx, const uint8_t *d_storage_roots, int su
 
     EvTimer leaf;
     HIP_CHECK(ctx, leaf.start(ctx->stream));
-    LAUNCH(ctx, k_leaf_account, grid_for(na), BLOCK, ctx->stream, ctx->d_acct, na,
+    LAUNCH(ctx, k_leaf_account, grid_for(na), BLOCK, ctx->stream, ctx->acct.d, na,
            d_storage_roots, lcp.as<int8_t>(), subtree, recs.as<node_rec>(),
            depths.as<uint8_t>(), hist.as<uint32_t>(), d_roots, d_child_refs,
            d_child_lens, nullptr, nullptr, nullptr, 0);
@@ -4316,7 +4309,7 @@ static int run_account_pass(sre_ctx *ctx, const uint8_t *d_storage_roots, int su
     in.recs = recs.as<node_rec>();
     in.depths = depths.as<uint8_t>();
     in.lcp = lcp.as<int8_t>();
-    in.keys = (const uint8_t *)ctx->d_acct + offsetof(sre_account_entry, key);
+    in.keys = (const uint8_t *)ctx->acct.d + offsetof(sre_account_entry, key);
     in.key_stride = sizeof(sre_account_entry);
     in.hist_host = hist_host;
     in.subtree = subtree;
@@ -4391,30 +4384,25 @@ static int proof_lookup_launch(sre_ctx *ctx, proof_lookup &l,
                                const uint8_t *keys, uint32_t klen, uint32_t n_t)
 {
     l.n = n_t;
-    HIP_CHECK(ctx, l.dkeys.alloc((uint64_t)klen * n_t));
-    HIP_CHECK(ctx, hipMemcpyAsync(l.dkeys.p, keys, (uint64_t)klen * n_t,
-                                  hipMemcpyHostToDevice, ctx->stream));
+    if (to_device(ctx, l.dkeys, keys, (uint64_t)klen * n_t))
+        return -1;
     HIP_CHECK(ctx, l.dti.alloc(4ull * n_t));
     HIP_CHECK(ctx, l.dpres.alloc(4ull * n_t));
     if (klen == 32)
-        LAUNCH(ctx, k_proof_ti, grid_for(n_t), BLOCK, ctx->stream, ctx->d_acct,
-               ctx->na, l.dkeys.as<uint8_t>(), n_t, l.dti.as<uint32_t>(),
+        LAUNCH(ctx, k_proof_ti, grid_for(n_t), BLOCK, ctx->stream, ctx->acct.d,
+               ctx->acct.n, l.dkeys.as<uint8_t>(), n_t, l.dti.as<uint32_t>(),
                l.dpres.as<uint32_t>());
     else
-        LAUNCH(ctx, k_proof_ti64, grid_for(n_t), BLOCK, ctx->stream, ctx->d_st,
-               ctx->ns, l.dkeys.as<uint8_t>(), n_t, l.dti.as<uint32_t>(),
+        LAUNCH(ctx, k_proof_ti64, grid_for(n_t), BLOCK, ctx->stream, ctx->st.d,
+               ctx->st.n, l.dkeys.as<uint8_t>(), n_t, l.dti.as<uint32_t>(),
                l.dpres.as<uint32_t>());
     return 0;
 }
 
 static int proof_lookup_fetch(sre_ctx *ctx, proof_lookup &l)
 {
-    l.ti.resize(l.n);
-    l.pres.resize(l.n);
-    HIP_CHECK(ctx, hipMemcpy(l.ti.data(), l.dti.p, 4ull * l.n,
-                             hipMemcpyDeviceToHost));
-    HIP_CHECK(ctx, hipMemcpy(l.pres.data(), l.dpres.p, 4ull * l.n,
-                             hipMemcpyDeviceToHost));
+    if (to_host(ctx, l.ti, l.dti, l.n) || to_host(ctx, l.pres, l.dpres, l.n))
+        return -1;
     return 0;
 }
 
@@ -4445,7 +4433,7 @@ struct proof_call {
     {
         if (alloc_err_flag(ctx, err))
             return -1;
-        HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
+        HIP_CHECK(ctx, acct_roots.alloc(ctx->acct.n * 32));
         return 0;
     }
 
@@ -4455,14 +4443,13 @@ struct proof_call {
         // exclusion targets also need the LEFT neighbour's path: a target
         // that sorts after every key of the divergent subtree has its lookup
         // path under index ti-1, not ti
-        HIP_CHECK(ctx, dti2.alloc(4ull * n_t));
         {
             std::vector<uint32_t> ti2(n_t);
             for (uint32_t t = 0; t < n_t; ++t)
                 ti2[t] = (!tgt.pres[t] && tgt.ti[t] > 0) ? tgt.ti[t] - 1
                                                          : tgt.ti[t];
-            HIP_CHECK(ctx, hipMemcpyAsync(dti2.p, ti2.data(), 4ull * n_t,
-                                          hipMemcpyHostToDevice, ctx->stream));
+            if (to_device(ctx, dti2, ti2.data(), n_t))
+                return -1;
         }
         uint32_t cap_rows = n_t * 260 + 64;
         HIP_CHECK(ctx, drows.alloc((uint64_t)cap_rows * sizeof(proof_row)));
@@ -4483,11 +4470,8 @@ struct proof_call {
             return -1;
         uint32_t nrows = 0;
         HIP_CHECK(ctx, hipMemcpy(&nrows, dcount.p, 4, hipMemcpyDeviceToHost));
-        rows.resize(nrows);
-        if (nrows)
-            HIP_CHECK(ctx, hipMemcpy(rows.data(), drows.p,
-                                     (uint64_t)nrows * sizeof(proof_row),
-                                     hipMemcpyDeviceToHost));
+        if (to_host(ctx, rows, drows, nrows))
+            return -1;
         per.resize(tgt.n);
         for (const auto &r : rows)
             per[r.target].push_back(&r);
@@ -4541,7 +4525,7 @@ extern "C" int sre_account_proof(sre_ctx *ctx, const uint8_t *targets,
         set_err(ctx, "sre_account_proof: 1..4096 targets");
         return -1;
     }
-    if (ctx->na == 0) { // empty trie: every proof is the empty node list
+    if (ctx->acct.n == 0) { // empty trie: every proof is the empty node list
         for (uint64_t t = 0; t < n_targets; ++t)
             out_counts[t] = 0;
         return 0;
@@ -4576,7 +4560,7 @@ extern "C" int sre_account_proof(sre_ctx *ctx, const uint8_t *targets,
         // candidate leaves: the accounts at ti / ti-1
         uint32_t cands[2];
         int ncand = 0;
-        cands[ncand++] = ti[t] < ctx->na ? ti[t] : (uint32_t)(ctx->na - 1);
+        cands[ncand++] = ti[t] < ctx->acct.n ? ti[t] : (uint32_t)(ctx->acct.n - 1);
         if (!pres[t] && ti[t] > 0 && ti[t] - 1 != cands[0])
             cands[ncand++] = ti[t] - 1;
         std::vector<std::vector<uint8_t>> leaves;
@@ -4586,7 +4570,7 @@ extern "C" int sre_account_proof(sre_ctx *ctx, const uint8_t *targets,
             uint8_t sroot[32];
             HIP_CHECK(ctx,
                       hipMemcpy(&ae,
-                                (const uint8_t *)ctx->d_acct +
+                                (const uint8_t *)ctx->acct.d +
                                     (uint64_t)idx * sizeof(sre_account_entry),
                                 sizeof(ae), hipMemcpyDeviceToHost));
             HIP_CHECK(ctx, hipMemcpy(sroot, acct_roots + 32ull * idx, 32,
@@ -4613,7 +4597,7 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
 {
     if (begin_call(ctx, false))
         return -1;
-    if (ctx->na == 0 || ctx->ns == 0) {
+    if (ctx->acct.n == 0 || ctx->st.n == 0) {
         set_err(ctx, "sre_storage_proof: no storage resident");
         return -1;
     }
@@ -4675,7 +4659,7 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
         // segment (a neighbour index may belong to another storage trie)
         uint32_t cands[2];
         int ncand = 0;
-        if (ti[t] < ctx->ns)
+        if (ti[t] < ctx->st.n)
             cands[ncand++] = ti[t];
         if (!pres[t] && ti[t] > 0)
             cands[ncand++] = ti[t] - 1;
@@ -4685,7 +4669,7 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
             sre_storage_entry se;
             HIP_CHECK(ctx,
                       hipMemcpy(&se,
-                                (const uint8_t *)ctx->d_st +
+                                (const uint8_t *)ctx->st.d +
                                     (uint64_t)idx * sizeof(sre_storage_entry),
                                 sizeof(se), hipMemcpyDeviceToHost));
             if (memcmp(se.acct_key, acct_keys + 32ull * t, 32) != 0)
@@ -4705,8 +4689,8 @@ extern "C" int sre_root(sre_ctx *ctx, uint8_t out_root[32])
 {
     if (begin_call(ctx, true))
         return -1;
-    if (ctx->na == 0) {
-        if (ctx->ns != 0) {
+    if (ctx->acct.n == 0) {
+        if (ctx->st.n != 0) {
             set_err(ctx, "storage entries without accounts");
             return -1;
         }
@@ -4719,7 +4703,7 @@ extern "C" int sre_root(sre_ctx *ctx, uint8_t out_root[32])
     DBuf err(ctx), acct_roots(ctx), root(ctx);
     if (alloc_err_flag(ctx, err))
         return -1;
-    HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
+    HIP_CHECK(ctx, acct_roots.alloc(ctx->acct.n * 32));
     HIP_CHECK(ctx, root.alloc(32));
 
     pass_out po;
@@ -4745,7 +4729,7 @@ extern "C" int sre_storage_roots(sre_ctx *ctx, uint8_t *out, uint64_t n)
 {
     if (begin_call(ctx, false))
         return -1;
-    if (n != ctx->na) {
+    if (n != ctx->acct.n) {
         set_err(ctx, "sre_storage_roots: n != uploaded account count");
         return -1;
     }
@@ -4754,13 +4738,13 @@ extern "C" int sre_storage_roots(sre_ctx *ctx, uint8_t *out, uint64_t n)
     DBuf err(ctx), acct_roots(ctx);
     if (alloc_err_flag(ctx, err))
         return -1;
-    HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
+    HIP_CHECK(ctx, acct_roots.alloc(ctx->acct.n * 32));
     pass_out po;
     if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &po, err.as<uint32_t>()))
         return -1;
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
-    HIP_CHECK(ctx, hipMemcpy(out, acct_roots.p, ctx->na * 32, hipMemcpyDeviceToHost));
+    HIP_CHECK(ctx, hipMemcpy(out, acct_roots.p, ctx->acct.n * 32, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -4772,7 +4756,7 @@ extern "C" int sre_subtree_roots(sre_ctx *ctx, uint8_t out_child_refs[16][33],
         return -1;
     memset(out_child_lens, 0, 16);
     memset(out_counts, 0, 16 * 8);
-    if (ctx->na == 0)
+    if (ctx->acct.n == 0)
         return 0;
     EvTimer whole;
     HIP_CHECK(ctx, whole.start(ctx->stream));
@@ -4780,7 +4764,7 @@ extern "C" int sre_subtree_roots(sre_ctx *ctx, uint8_t out_child_refs[16][33],
     DBuf err(ctx), acct_roots(ctx), roots(ctx), crefs(ctx), clens(ctx), counts(ctx);
     if (alloc_err_flag(ctx, err))
         return -1;
-    HIP_CHECK(ctx, acct_roots.alloc(ctx->na * 32));
+    HIP_CHECK(ctx, acct_roots.alloc(ctx->acct.n * 32));
     HIP_CHECK(ctx, roots.alloc(16 * 32));
     HIP_CHECK(ctx, crefs.alloc(16 * 33));
     HIP_CHECK(ctx, clens.alloc(16));
@@ -4799,8 +4783,8 @@ extern "C" int sre_subtree_roots(sre_ctx *ctx, uint8_t out_child_refs[16][33],
                          crefs.as<uint8_t>(), clens.as<uint8_t>(), &po,
                          err.as<uint32_t>()))
         return -1;
-    LAUNCH(ctx, k_nibble_counts, grid_for(ctx->na), BLOCK, ctx->stream,
-           ctx->d_acct, ctx->na, counts.as<uint64_t>());
+    LAUNCH(ctx, k_nibble_counts, grid_for(ctx->acct.n), BLOCK, ctx->stream,
+           ctx->acct.d, ctx->acct.n, counts.as<uint64_t>());
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
     HIP_CHECK(ctx, whole.stop(ctx->stream));
@@ -4860,254 +4844,229 @@ static uint64_t sds_min_ns()
     return e ? (uint64_t)atoll(e) : (1ull << 20);
 }
 
-static int apply_delta_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
-                            uint64_t n_acct, const sre_storage_entry *st_delta,
-                            uint64_t n_st, DBuf *map_out /* optional: old->new
-                            positions, (old na)+1 u32 */,
-                            const uint8_t *d_old_roots = nullptr,
-                            uint8_t *d_new_roots = nullptr /* carry retained
-                            storage roots across the merge (new-na x 32,
-                            pre-filled EMPTY by the caller) */,
-                            bool *st_closed_form = nullptr /* optional: set
-                            when the closed-form storage merge ran */)
-{
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    uint64_t nb = ctx->na, ns = ctx->ns;
-    DBuf dl_a(ctx), dl_s(ctx), err(ctx);
-    DBuf fa(ctx), fd(ctx), fdel(ctx), sa(ctx), sd(ctx), sdel(ctx);
-    if (alloc_err_flag(ctx, err))
-        return -1;
-    HIP_CHECK(ctx, dl_a.alloc((n_acct ? n_acct : 1) * sizeof(sre_account_delta)));
-    HIP_CHECK(ctx, dl_s.alloc((n_st ? n_st : 1) * sizeof(sre_storage_entry)));
-    if (n_acct)
-        HIP_CHECK(ctx, hipMemcpyAsync(dl_a.p, acct_delta,
-                                      n_acct * sizeof(sre_account_delta),
-                                      hipMemcpyHostToDevice, ctx->stream));
-    if (n_st)
-        HIP_CHECK(ctx, hipMemcpyAsync(dl_s.p, st_delta,
-                                      n_st * sizeof(sre_storage_entry),
-                                      hipMemcpyHostToDevice, ctx->stream));
+// Optional extras of a delta merge, and what it reports back.
+struct merge_io {
+    DBuf *map_out = nullptr; // old->new positions, (old na)+1 u32
+    // carry retained storage roots across the merge (d_new_roots: new-na x
+    // 32, pre-filled EMPTY by the caller)
+    const uint8_t *d_old_roots = nullptr;
+    uint8_t *d_new_roots = nullptr;
+    bool st_closed_form = false; // result: the closed-form storage merge ran
+};
 
-    // ---- accounts ----
+// What the steps of the general delta merge share: the uploaded delta, the
+// error flag, the destroyed accounts' keys and the merged arrays, which
+// stay the DBufs' (so any failing return gives them back) until
+// adopt_merged installs them.
+struct delta_merge {
+    sre_ctx *ctx;
+    const sre_account_delta *acct_delta;
+    uint64_t n_acct;
+    const sre_storage_entry *st_delta;
+    uint64_t n_st;
+    DBuf dl_a{ctx}, dl_s{ctx}, err{ctx}, sdel{ctx}, new_acct{ctx}, new_st{ctx};
+    uint32_t n_del = 0; // destroyed accounts (keys in sdel)
+    uint64_t new_na = 0, new_ns = 0;
+};
+
+// Pool buffer for a merged array of n rows. The count meets the u32
+// capacity contract (check_cap) before anything is allocated.
+static int alloc_merged(sre_ctx *ctx, DBuf &out, uint64_t n, size_t row_bytes,
+                        const char *oom)
+{
+    if (check_cap(ctx, n))
+        return -1;
+    if (out.alloc((n ? n : 1) * row_bytes) != hipSuccess) {
+        set_err(ctx, oom);
+        return -1;
+    }
+    return 0;
+}
+
+// Tail of every delta merge: the merged arrays become the resident state.
+// An empty st means the storage array was not merged and stays in place.
+static void adopt_merged(sre_ctx *ctx, DBuf &acct, uint64_t na, DBuf &st,
+                         uint64_t ns)
+{
+    const size_t adopted[2] = {acct.sz, st.p ? st.sz : 0};
+    ctx->acct.adopt(ctx, acct, na);
+    if (st.p)
+        ctx->st.adopt(ctx, st, ns);
+    // prewarm the ping-pong partner buffers: the NEXT delta would otherwise
+    // pay a multi-hundred-ms first-time hipMalloc of this size class inside
+    // the caller's timed region
+    for (size_t b : adopted) {
+        DBuf spare(ctx);
+        if (b)
+            (void)spare.alloc(b);
+    }
+}
+
+static int merge_accounts_general(delta_merge &m, const merge_io &io)
+{
+    sre_ctx *ctx = m.ctx;
+    uint64_t nb = ctx->acct.n, n_acct = m.n_acct;
+    const sre_account_delta *dl_a = m.dl_a.as<sre_account_delta>();
+    uint32_t *d_err = m.err.as<uint32_t>();
+    DBuf fa(ctx), fd(ctx), fdel(ctx), ea(ctx), ed(ctx), edel(ctx);
     HIP_CHECK(ctx, fa.alloc((nb + 1) * 4));
     HIP_CHECK(ctx, fd.alloc((n_acct + 1) * 4));
     HIP_CHECK(ctx, fdel.alloc((n_acct + 1) * 4));
     LAUNCH(ctx, k_ovl_base_acct_flags, grid_for(nb + 1), BLOCK, ctx->stream,
-           ctx->d_acct, nb, dl_a.as<sre_account_delta>(), n_acct,
-           fa.as<uint32_t>());
+           ctx->acct.d, nb, dl_a, n_acct, fa.as<uint32_t>());
     LAUNCH(ctx, k_ovl_delta_acct_flags, grid_for(n_acct + 1), BLOCK, ctx->stream,
-           dl_a.as<sre_account_delta>(), n_acct, fd.as<uint32_t>(),
-           fdel.as<uint32_t>(), err.as<uint32_t>());
-    uint32_t Bk = 0, Dk = 0, Ndel = 0;
-    DBuf ea(ctx), ed(ctx), edel(ctx);
+           dl_a, n_acct, fd.as<uint32_t>(), fdel.as<uint32_t>(), d_err);
+    uint32_t Bk = 0, Dk = 0;
     HIP_CHECK(ctx, ea.alloc((nb + 1) * 4));
     HIP_CHECK(ctx, ed.alloc((n_acct + 1) * 4));
     HIP_CHECK(ctx, edel.alloc((n_acct + 1) * 4));
-    if (scan_u32(ctx, fa.as<uint32_t>(), ea.as<uint32_t>(), nb + 1, &Bk))
+    if (scan_u32(ctx, fa.as<uint32_t>(), ea.as<uint32_t>(), nb + 1, &Bk) ||
+        scan_u32(ctx, fd.as<uint32_t>(), ed.as<uint32_t>(), n_acct + 1, &Dk) ||
+        scan_u32(ctx, fdel.as<uint32_t>(), edel.as<uint32_t>(), n_acct + 1,
+                 &m.n_del) ||
+        check_err(ctx, d_err))
         return -1;
-    if (scan_u32(ctx, fd.as<uint32_t>(), ed.as<uint32_t>(), n_acct + 1, &Dk))
+    m.new_na = merged_count(Bk, Dk);
+    if (alloc_merged(ctx, m.new_acct, m.new_na, sizeof(sre_account_entry),
+                     "apply_delta: out of memory (accounts)"))
         return -1;
-    if (scan_u32(ctx, fdel.as<uint32_t>(), edel.as<uint32_t>(), n_acct + 1, &Ndel))
-        return -1;
-    if (check_err(ctx, err.as<uint32_t>()))
-        return -1;
-    uint64_t new_na = Bk + Dk;
-    size_t acct_bytes = (new_na ? new_na : 1) * sizeof(sre_account_entry);
-    void *new_acct = pool_get(ctx, acct_bytes);
-    if (!new_acct) {
-        set_err(ctx, "apply_delta: out of memory (accounts)");
-        return -1;
-    }
     uint64_t gmax = nb > n_acct ? nb : n_acct;
     if (gmax)
         LAUNCH(ctx, k_ovl_scatter_acct, grid_for(gmax), BLOCK, ctx->stream,
-               ctx->d_acct, nb, ea.as<uint32_t>(), dl_a.as<sre_account_delta>(),
-               n_acct, ed.as<uint32_t>(), (sre_account_entry *)new_acct);
-    if (map_out) {
-        HIP_CHECK(ctx, map_out->alloc((nb + 1) * 4));
+               ctx->acct.d, nb, ea.as<uint32_t>(), dl_a, n_acct,
+               ed.as<uint32_t>(), m.new_acct.as<sre_account_entry>());
+    if (io.map_out) {
+        HIP_CHECK(ctx, io.map_out->alloc((nb + 1) * 4));
         LAUNCH(ctx, k_ovl_posmap, grid_for(nb + 1), BLOCK, ctx->stream,
-               ctx->d_acct, nb, ea.as<uint32_t>(), dl_a.as<sre_account_delta>(),
-               n_acct, ed.as<uint32_t>(), map_out->as<uint32_t>());
+               ctx->acct.d, nb, ea.as<uint32_t>(), dl_a, n_acct,
+               ed.as<uint32_t>(), io.map_out->as<uint32_t>());
     }
-    if (d_old_roots && d_new_roots && nb)
+    if (io.d_old_roots && io.d_new_roots && nb)
         LAUNCH(ctx, k_ovl_carry_roots, grid_for(nb), BLOCK, ctx->stream,
-               ctx->d_acct, nb, ea.as<uint32_t>(), dl_a.as<sre_account_delta>(),
-               n_acct, ed.as<uint32_t>(), d_old_roots, d_new_roots);
-    HIP_CHECK(ctx, sdel.alloc((Ndel ? Ndel : 1) * 32));
+               ctx->acct.d, nb, ea.as<uint32_t>(), dl_a, n_acct,
+               ed.as<uint32_t>(), io.d_old_roots, io.d_new_roots);
+    HIP_CHECK(ctx, m.sdel.alloc((m.n_del ? m.n_del : 1) * 32));
     if (n_acct)
         LAUNCH(ctx, k_ovl_gather_deleted, grid_for(n_acct), BLOCK, ctx->stream,
-               dl_a.as<sre_account_delta>(), n_acct, edel.as<uint32_t>(),
-               sdel.as<uint8_t>());
+               dl_a, n_acct, edel.as<uint32_t>(), m.sdel.as<uint8_t>());
+    return 0;
+}
 
-    // ---- storage ----
-    uint64_t new_ns = 0;
-    size_t st_bytes = 0;
-    void *new_st = nullptr;
-    bool st_done = false, keep_st = false;
-    if (ns && n_st == 0 && Ndel == 0 && ctx->own_st) {
+// Closed-form small-delta storage merge: delta ranks + wipe-range prefix
+// sums (merge_plan.h) instead of O(ns) flags/scans/posmap. The host
+// validates what k_ovl_delta_st_flags checks on device (the owner lookup
+// against the resident accounts rides in k_sds_marks).
+static int merge_storage_closed_form(delta_merge &m)
+{
+    sre_ctx *ctx = m.ctx;
+    uint64_t ns = ctx->st.n, n_st = m.n_st;
+    uint32_t n_del = m.n_del;
+    const sre_storage_entry *dl_s = m.dl_s.as<sre_storage_entry>();
+    if (uint32_t bad = st_delta_flags(m.st_delta, n_st,
+                                      deleted_accounts(m.acct_delta, m.n_acct)))
+        return fail_flags(ctx, bad);
+    DBuf bpos(ctx), match(ctx), mex(ctx), eex(ctx), dwlo(ctx), dwhi(ctx),
+        dwsum(ctx);
+    HIP_CHECK(ctx, bpos.alloc((n_st ? n_st : 1) * 4));
+    HIP_CHECK(ctx, match.alloc((n_st ? n_st : 1) * 4));
+    if (n_st)
+        LAUNCH(ctx, k_sds_marks, grid_for(n_st), BLOCK, ctx->stream, ctx->st.d,
+               ns, dl_s, n_st, ctx->acct.d, ctx->acct.n,
+               m.dl_a.as<sre_account_delta>(), m.n_acct, bpos.as<uint32_t>(),
+               match.as<uint32_t>());
+    HIP_CHECK(ctx, dwlo.alloc((n_del ? n_del : 1) * 4));
+    HIP_CHECK(ctx, dwhi.alloc((n_del ? n_del : 1) * 4));
+    if (n_del)
+        LAUNCH(ctx, k_sds_wipes, grid_for(n_del), BLOCK, ctx->stream, ctx->st.d,
+               ns, m.sdel.as<uint8_t>(), n_del, dwlo.as<uint32_t>(),
+               dwhi.as<uint32_t>());
+    std::vector<uint32_t> match_h, wlo_h, whi_h;
+    if (to_host(ctx, match_h, match, n_st) || to_host(ctx, wlo_h, dwlo, n_del) ||
+        to_host(ctx, whi_h, dwhi, n_del))
+        return -1;
+    merge_plan pl;
+    if (uint32_t bad = plan_st_small(ns, m.st_delta, n_st, match_h, wlo_h, whi_h, pl))
+        return fail_flags(ctx, bad); // nothing adopted
+    m.new_ns = pl.new_n;
+    if (alloc_merged(ctx, m.new_st, m.new_ns, sizeof(sre_storage_entry),
+                     "apply_delta: out of memory (storage)") ||
+        to_device(ctx, mex, pl.m_excl.data(), n_st + 1) ||
+        to_device(ctx, eex, pl.eff_excl.data(), n_st + 1) ||
+        to_device(ctx, dwsum, pl.wsum.data(), (uint64_t)n_del + 1))
+        return -1;
+    LAUNCH(ctx, k_sds_scatter, grid_for(ns), BLOCK, ctx->stream, ctx->st.d, ns,
+           dl_s, n_st, mex.as<uint32_t>(), eex.as<uint32_t>(),
+           dwlo.as<uint32_t>(), dwhi.as<uint32_t>(), dwsum.as<uint32_t>(), n_del,
+           m.new_st.as<sre_storage_entry>());
+    if (n_st)
+        LAUNCH(ctx, k_sds_place, grid_for(n_st), BLOCK, ctx->stream, dl_s, n_st,
+               bpos.as<uint32_t>(), mex.as<uint32_t>(), eex.as<uint32_t>(),
+               dwlo.as<uint32_t>(), dwhi.as<uint32_t>(), dwsum.as<uint32_t>(),
+               n_del, m.new_st.as<sre_storage_entry>());
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+static int merge_storage_general(delta_merge &m)
+{
+    sre_ctx *ctx = m.ctx;
+    uint64_t ns = ctx->st.n, n_st = m.n_st;
+    const sre_storage_entry *dl_s = m.dl_s.as<sre_storage_entry>();
+    DBuf sa(ctx), sd(ctx), esa(ctx), esd(ctx);
+    HIP_CHECK(ctx, sa.alloc((ns + 1) * 4));
+    HIP_CHECK(ctx, sd.alloc((n_st + 1) * 4));
+    LAUNCH(ctx, k_ovl_base_st_flags, grid_for(ns + 1), BLOCK, ctx->stream,
+           ctx->st.d, ns, dl_s, n_st, m.sdel.as<uint8_t>(), (uint64_t)m.n_del,
+           sa.as<uint32_t>());
+    LAUNCH(ctx, k_ovl_delta_st_flags, grid_for(n_st + 1), BLOCK, ctx->stream,
+           dl_s, n_st, m.sdel.as<uint8_t>(), (uint64_t)m.n_del, ctx->acct.d,
+           ctx->acct.n, m.dl_a.as<sre_account_delta>(), m.n_acct,
+           sd.as<uint32_t>(), m.err.as<uint32_t>());
+    uint32_t Sk = 0, Tk = 0;
+    HIP_CHECK(ctx, esa.alloc((ns + 1) * 4));
+    HIP_CHECK(ctx, esd.alloc((n_st + 1) * 4));
+    if (scan_u32(ctx, sa.as<uint32_t>(), esa.as<uint32_t>(), ns + 1, &Sk) ||
+        scan_u32(ctx, sd.as<uint32_t>(), esd.as<uint32_t>(), n_st + 1, &Tk) ||
+        check_err(ctx, m.err.as<uint32_t>()))
+        return -1;
+    m.new_ns = merged_count(Sk, Tk);
+    if (alloc_merged(ctx, m.new_st, m.new_ns, sizeof(sre_storage_entry),
+                     "apply_delta: out of memory (storage)"))
+        return -1;
+    uint64_t gmax = ns > n_st ? ns : n_st;
+    if (gmax)
+        LAUNCH(ctx, k_ovl_scatter_st, grid_for(gmax), BLOCK, ctx->stream,
+               ctx->st.d, ns, esa.as<uint32_t>(), dl_s, n_st,
+               esd.as<uint32_t>(), m.new_st.as<sre_storage_entry>());
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// General overlay merge of a delta into the resident state: accounts, then
+// whichever storage merge fits, then adoption.
+static int merge_delta(sre_ctx *ctx, const sre_account_delta *acct_delta,
+                       uint64_t n_acct, const sre_storage_entry *st_delta,
+                       uint64_t n_st, merge_io &io)
+{
+    HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    delta_merge m{ctx, acct_delta, n_acct, st_delta, n_st};
+    if (alloc_err_flag(ctx, m.err) || to_device(ctx, m.dl_a, acct_delta, n_acct) ||
+        to_device(ctx, m.dl_s, st_delta, n_st) || merge_accounts_general(m, io))
+        return -1;
+    uint64_t ns = ctx->st.n;
+    if (ns && n_st == 0 && m.n_del == 0 && ctx->st.own) {
         // accounts-only delta over a storage-bearing state: the storage
-        // array is untouched — keep it in place (engine-owned only: a
-        // borrowed array may be released by the caller after the delta)
-        new_ns = ns;
-        st_done = keep_st = true;
-    } else if (ns > sds_min_ns() && n_st <= (ns >> 8) &&
-               (uint64_t)Ndel <= 4096) {
-        // closed-form small-delta storage merge: delta ranks + wipe-range
-        // prefix sums instead of O(ns) flags/scans/posmap. Host-side
-        // validation of what k_ovl_delta_st_flags checked on device (the
-        // owner lookup against the resident accounts rides in k_sds_marks).
-        uint32_t bad = 0;
-        std::vector<key32> dead = deleted_accounts(acct_delta, n_acct);
-        for (uint64_t i = 0; i < n_st; ++i) {
-            if (i && memcmp(&st_delta[i - 1], &st_delta[i], 64) >= 0)
-                bad |= 1u << E_UNSORTED_STORAGE; // or duplicate (acct,slot)
-            if (key_in(dead, st_delta[i].acct_key))
-                bad |= 1u << E_ORPHAN_STORAGE; // row for a destroyed account
-        }
-        if (bad) {
-            pool_put(ctx, acct_bytes, new_acct);
-            return fail_flags(ctx, bad);
-        }
-        DBuf bpos(ctx), match(ctx), mex(ctx), eex(ctx), dwlo(ctx), dwhi(ctx),
-            dwsum(ctx);
-        HIP_CHECK(ctx, bpos.alloc((n_st ? n_st : 1) * 4));
-        HIP_CHECK(ctx, match.alloc((n_st ? n_st : 1) * 4));
-        if (n_st)
-            LAUNCH(ctx, k_sds_marks, grid_for(n_st), BLOCK, ctx->stream,
-                   ctx->d_st, ns, dl_s.as<sre_storage_entry>(), n_st,
-                   ctx->d_acct, nb, dl_a.as<sre_account_delta>(), n_acct,
-                   bpos.as<uint32_t>(), match.as<uint32_t>());
-        HIP_CHECK(ctx, dwlo.alloc((Ndel ? Ndel : 1) * 4));
-        HIP_CHECK(ctx, dwhi.alloc((Ndel ? Ndel : 1) * 4));
-        HIP_CHECK(ctx, dwsum.alloc(((uint64_t)Ndel + 1) * 4));
-        if (Ndel)
-            LAUNCH(ctx, k_sds_wipes, grid_for(Ndel), BLOCK, ctx->stream,
-                   ctx->d_st, ns, sdel.as<uint8_t>(), Ndel, dwlo.as<uint32_t>(),
-                   dwhi.as<uint32_t>());
-        std::vector<uint32_t> bpos_h(n_st), match_h(n_st), wlo_h(Ndel),
-            whi_h(Ndel), wsum_h(Ndel + 1);
-        if (n_st) {
-            HIP_CHECK(ctx, hipMemcpy(bpos_h.data(), bpos.p, 4 * n_st,
-                                     hipMemcpyDeviceToHost));
-            HIP_CHECK(ctx, hipMemcpy(match_h.data(), match.p, 4 * n_st,
-                                     hipMemcpyDeviceToHost));
-        }
-        for (uint64_t k = 0; k < n_st; ++k)
-            if (match_h[k] & SDS_ORPHAN) { // nothing adopted or allocated yet
-                pool_put(ctx, acct_bytes, new_acct);
-                return fail_flags(ctx, 1u << E_ORPHAN_STORAGE);
-            }
-        if (Ndel) {
-            HIP_CHECK(ctx, hipMemcpy(wlo_h.data(), dwlo.p, 4ull * Ndel,
-                                     hipMemcpyDeviceToHost));
-            HIP_CHECK(ctx, hipMemcpy(whi_h.data(), dwhi.p, 4ull * Ndel,
-                                     hipMemcpyDeviceToHost));
-        }
-        wsum_h[0] = 0;
-        for (uint32_t a = 0; a < Ndel; ++a)
-            wsum_h[a + 1] = wsum_h[a] + (whi_h[a] - wlo_h[a]);
-        std::vector<uint32_t> mex_h(n_st + 1), eex_h(n_st + 1);
-        mex_h[0] = eex_h[0] = 0;
-        for (uint64_t k = 0; k < n_st; ++k) {
-            bool nz = false;
-            for (int q = 0; q < 32; ++q)
-                nz |= st_delta[k].value[q] != 0;
-            mex_h[k + 1] = mex_h[k] + ((match_h[k] & SDS_MATCH) ? 1 : 0);
-            eex_h[k + 1] = eex_h[k] + (nz ? 1 : 0);
-        }
-        new_ns = ns - mex_h[n_st] - wsum_h[Ndel] + eex_h[n_st];
-        HIP_CHECK(ctx, mex.alloc(4 * (n_st + 1)));
-        HIP_CHECK(ctx, eex.alloc(4 * (n_st + 1)));
-        HIP_CHECK(ctx, hipMemcpyAsync(mex.p, mex_h.data(), 4 * (n_st + 1),
-                                      hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK(ctx, hipMemcpyAsync(eex.p, eex_h.data(), 4 * (n_st + 1),
-                                      hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK(ctx, hipMemcpyAsync(dwsum.p, wsum_h.data(),
-                                      4ull * (Ndel + 1),
-                                      hipMemcpyHostToDevice, ctx->stream));
-        st_bytes = (new_ns ? new_ns : 1) * sizeof(sre_storage_entry);
-        new_st = pool_get(ctx, st_bytes);
-        if (!new_st) {
-            pool_put(ctx, acct_bytes, new_acct);
-            set_err(ctx, "apply_delta: out of memory (storage)");
+        // array is untouched and m.new_st stays empty, so it is kept in
+        // place (engine-owned only: a borrowed array may be released by
+        // the caller after the delta)
+    } else if (ns > sds_min_ns() && n_st <= (ns >> 8) && m.n_del <= 4096) {
+        if (merge_storage_closed_form(m))
             return -1;
-        }
-        LAUNCH(ctx, k_sds_scatter, grid_for(ns), BLOCK, ctx->stream, ctx->d_st,
-               ns, dl_s.as<sre_storage_entry>(), n_st, mex.as<uint32_t>(),
-               eex.as<uint32_t>(), dwlo.as<uint32_t>(), dwhi.as<uint32_t>(),
-               dwsum.as<uint32_t>(), Ndel, (sre_storage_entry *)new_st);
-        if (n_st)
-            LAUNCH(ctx, k_sds_place, grid_for(n_st), BLOCK, ctx->stream,
-                   dl_s.as<sre_storage_entry>(), n_st, bpos.as<uint32_t>(),
-                   mex.as<uint32_t>(), eex.as<uint32_t>(), dwlo.as<uint32_t>(),
-                   dwhi.as<uint32_t>(), dwsum.as<uint32_t>(), Ndel,
-                   (sre_storage_entry *)new_st);
-        HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        st_done = true;
-        if (st_closed_form)
-            *st_closed_form = true;
+        io.st_closed_form = true;
+    } else if (merge_storage_general(m)) {
+        return -1;
     }
-    if (!st_done) {
-        HIP_CHECK(ctx, sa.alloc((ns + 1) * 4));
-        HIP_CHECK(ctx, sd.alloc((n_st + 1) * 4));
-        LAUNCH(ctx, k_ovl_base_st_flags, grid_for(ns + 1), BLOCK, ctx->stream,
-               ctx->d_st, ns, dl_s.as<sre_storage_entry>(), n_st,
-               sdel.as<uint8_t>(), (uint64_t)Ndel, sa.as<uint32_t>());
-        LAUNCH(ctx, k_ovl_delta_st_flags, grid_for(n_st + 1), BLOCK, ctx->stream,
-               dl_s.as<sre_storage_entry>(), n_st, sdel.as<uint8_t>(),
-               (uint64_t)Ndel, ctx->d_acct, nb, dl_a.as<sre_account_delta>(),
-               n_acct, sd.as<uint32_t>(), err.as<uint32_t>());
-        uint32_t Sk = 0, Tk = 0;
-        DBuf esa(ctx), esd(ctx);
-        HIP_CHECK(ctx, esa.alloc((ns + 1) * 4));
-        HIP_CHECK(ctx, esd.alloc((n_st + 1) * 4));
-        if (scan_u32(ctx, sa.as<uint32_t>(), esa.as<uint32_t>(), ns + 1, &Sk))
-            return -1;
-        if (scan_u32(ctx, sd.as<uint32_t>(), esd.as<uint32_t>(), n_st + 1,
-                     &Tk))
-            return -1;
-        if (check_err(ctx, err.as<uint32_t>())) {
-            pool_put(ctx, acct_bytes, new_acct);
-            return -1;
-        }
-        new_ns = Sk + Tk;
-        st_bytes = (new_ns ? new_ns : 1) * sizeof(sre_storage_entry);
-        new_st = pool_get(ctx, st_bytes);
-        if (!new_st) {
-            pool_put(ctx, acct_bytes, new_acct);
-            set_err(ctx, "apply_delta: out of memory (storage)");
-            return -1;
-        }
-        gmax = ns > n_st ? ns : n_st;
-        if (gmax)
-            LAUNCH(ctx, k_ovl_scatter_st, grid_for(gmax), BLOCK, ctx->stream,
-                   ctx->d_st, ns, esa.as<uint32_t>(),
-                   dl_s.as<sre_storage_entry>(), n_st, esd.as<uint32_t>(),
-                   (sre_storage_entry *)new_st);
-        HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-
-    // adopt the merged state (pool-backed; reused across repeated deltas)
-    release_acct(ctx);
-    ctx->d_acct = (const sre_account_entry *)new_acct;
-    ctx->na = new_na;
-    ctx->own_acct = true;
-    ctx->acct_pool_bytes = acct_bytes;
-    if (!keep_st) { // keep_st: untouched storage array stays in place
-        release_st(ctx);
-        ctx->d_st = (const sre_storage_entry *)new_st;
-        ctx->ns = new_ns;
-        ctx->own_st = true;
-        ctx->st_pool_bytes = st_bytes;
-    }
-    // prewarm the ping-pong partner buffers: the NEXT apply_delta would
-    // otherwise pay a multi-hundred-ms first-time hipMalloc of this size
-    // class inside the caller's timed region
-    for (size_t b : {acct_bytes, keep_st ? acct_bytes : st_bytes}) {
-        void *spare = pool_get(ctx, b);
-        if (spare)
-            pool_put(ctx, b, spare);
-    }
+    adopt_merged(ctx, m.new_acct, m.new_na, m.new_st, m.new_ns);
     return 0;
 }
 
@@ -5117,7 +5076,8 @@ extern "C" int sre_apply_delta(sre_ctx *ctx,
                                const sre_storage_entry *st_delta, uint64_t n_st)
 {
     invalidate_retention(ctx); // a plain apply invalidates cell retention
-    return apply_delta_impl(ctx, acct_delta, n_acct, st_delta, n_st, nullptr);
+    merge_io io;
+    return merge_delta(ctx, acct_delta, n_acct, st_delta, n_st, io);
 }
 
 // Small-delta account merge + lcp repair (accounts-only dirty path): one
@@ -5128,97 +5088,60 @@ extern "C" int sre_apply_delta(sre_ctx *ctx,
 static int apply_delta_small(sre_ctx *ctx, const sre_account_delta *acct_delta,
                              uint64_t nd, DBuf *map_out)
 {
-    uint64_t nb = ctx->na;
+    uint64_t nb = ctx->acct.n;
     // the general path's k_ovl_delta_acct_flags validates this on device;
     // closed-form ranks would silently mis-merge on unsorted input
-    for (uint64_t k = 1; k < nd; ++k)
-        if (memcmp(acct_delta[k - 1].key, acct_delta[k].key, 32) >= 0)
-            return fail_flags(ctx, 1u << E_UNSORTED_ACCT);
+    if (uint32_t bad = acct_delta_order(acct_delta, nd))
+        return fail_flags(ctx, bad);
     DBuf dl(ctx), bpos(ctx), match(ctx), mex(ctx), eex(ctx), npos(ctx),
-        err(ctx);
-    HIP_CHECK(ctx, dl.alloc(nd * sizeof(sre_account_delta)));
-    HIP_CHECK(ctx, hipMemcpyAsync(dl.p, acct_delta,
-                                  nd * sizeof(sre_account_delta),
-                                  hipMemcpyHostToDevice, ctx->stream));
+        dpatch(ctx), err(ctx), out(ctx), no_st(ctx);
+    if (to_device(ctx, dl, acct_delta, nd))
+        return -1;
     HIP_CHECK(ctx, bpos.alloc(nd * 4));
     HIP_CHECK(ctx, match.alloc(nd * 4));
-    LAUNCH(ctx, k_sd_marks, grid_for(nd), BLOCK, ctx->stream, ctx->d_acct, nb,
+    LAUNCH(ctx, k_sd_marks, grid_for(nd), BLOCK, ctx->stream, ctx->acct.d, nb,
            dl.as<sre_account_delta>(), nd, bpos.as<uint32_t>(),
            match.as<uint32_t>());
-    std::vector<uint32_t> bpos_h(nd), match_h(nd);
-    HIP_CHECK(ctx, hipMemcpy(bpos_h.data(), bpos.p, 4 * nd,
-                             hipMemcpyDeviceToHost));
-    HIP_CHECK(ctx, hipMemcpy(match_h.data(), match.p, 4 * nd,
-                             hipMemcpyDeviceToHost));
-    std::vector<uint32_t> mex_h(nd + 1), eex_h(nd + 1);
-    mex_h[0] = eex_h[0] = 0;
-    for (uint64_t k = 0; k < nd; ++k) {
-        mex_h[k + 1] = mex_h[k] + (match_h[k] ? 1 : 0);
-        eex_h[k + 1] = eex_h[k] + (acct_delta[k].deleted ? 0 : 1);
-    }
-    uint64_t new_na = nb - mex_h[nd] + eex_h[nd];
-    HIP_CHECK(ctx, mex.alloc(4 * (nd + 1)));
-    HIP_CHECK(ctx, eex.alloc(4 * (nd + 1)));
-    HIP_CHECK(ctx, hipMemcpyAsync(mex.p, mex_h.data(), 4 * (nd + 1),
-                                  hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(ctx, hipMemcpyAsync(eex.p, eex_h.data(), 4 * (nd + 1),
-                                  hipMemcpyHostToDevice, ctx->stream));
-    size_t acct_bytes = (new_na ? new_na : 1) * sizeof(sre_account_entry);
-    void *out = pool_get(ctx, acct_bytes);
-    if (!out) {
-        set_err(ctx, "apply_delta_small: out of memory");
+    std::vector<uint32_t> match_h, npos_h;
+    if (to_host(ctx, match_h, match, nd))
         return -1;
-    }
+    merge_plan pl = plan_acct_small(nb, acct_delta, nd, match_h);
+    uint64_t new_na = pl.new_n;
+    if (alloc_merged(ctx, out, new_na, sizeof(sre_account_entry),
+                     "apply_delta_small: out of memory") ||
+        to_device(ctx, mex, pl.m_excl.data(), nd + 1) ||
+        to_device(ctx, eex, pl.eff_excl.data(), nd + 1))
+        return -1;
     HIP_CHECK(ctx, map_out->alloc((nb + 1) * 4));
-    LAUNCH(ctx, k_sd_scatter, grid_for(nb + 1), BLOCK, ctx->stream, ctx->d_acct,
+    LAUNCH(ctx, k_sd_scatter, grid_for(nb + 1), BLOCK, ctx->stream, ctx->acct.d,
            nb, dl.as<sre_account_delta>(), nd, mex.as<uint32_t>(),
-           eex.as<uint32_t>(), (sre_account_entry *)out,
+           eex.as<uint32_t>(), out.as<sre_account_entry>(),
            map_out->as<uint32_t>());
     HIP_CHECK(ctx, npos.alloc(nd * 4));
     LAUNCH(ctx, k_sd_place, grid_for(nd), BLOCK, ctx->stream,
            dl.as<sre_account_delta>(), nd, bpos.as<uint32_t>(),
-           mex.as<uint32_t>(), eex.as<uint32_t>(), (sre_account_entry *)out,
+           mex.as<uint32_t>(), eex.as<uint32_t>(), out.as<sre_account_entry>(),
            npos.as<uint32_t>());
     // lcp repair into the ping-pong partner
-    if (grow_retained(ctx, &ctx->d_lcp_ret2, &ctx->lcp_ret2_capacity,
-                      new_na + 1))
+    if (ctx->lcp_ret2.grow(ctx, new_na + 1))
         return -1;
     LAUNCH(ctx, k_sd_lcp_copy, grid_for(nb), BLOCK, ctx->stream,
-           map_out->as<uint32_t>(), nb, (const int8_t *)ctx->d_lcp_ret,
-           (int8_t *)ctx->d_lcp_ret2);
-    std::vector<uint32_t> npos_h(nd);
-    HIP_CHECK(ctx, hipMemcpy(npos_h.data(), npos.p, 4 * nd,
-                             hipMemcpyDeviceToHost));
-    std::vector<uint32_t> patch;
-    patch.reserve(2 * nd + 2);
-    patch.push_back(0);
-    patch.push_back((uint32_t)new_na);
-    for (uint64_t k = 0; k < nd; ++k) {
-        patch.push_back(npos_h[k]); // insert/replace pos; delete junction
-        if (!acct_delta[k].deleted)
-            patch.push_back(npos_h[k] + 1);
-    }
-    std::sort(patch.begin(), patch.end());
-    patch.erase(std::unique(patch.begin(), patch.end()), patch.end());
-    DBuf dpatch(ctx);
-    HIP_CHECK(ctx, dpatch.alloc(4 * patch.size()));
-    HIP_CHECK(ctx, hipMemcpyAsync(dpatch.p, patch.data(), 4 * patch.size(),
-                                  hipMemcpyHostToDevice, ctx->stream));
-    if (alloc_err_flag(ctx, err))
+           map_out->as<uint32_t>(), nb, (const int8_t *)ctx->lcp_ret.p,
+           (int8_t *)ctx->lcp_ret2.p);
+    if (to_host(ctx, npos_h, npos, nd))
+        return -1;
+    std::vector<uint32_t> patch = lcp_patch_list(acct_delta, nd, npos_h, new_na);
+    if (to_device(ctx, dpatch, patch.data(), patch.size()) ||
+        alloc_err_flag(ctx, err))
         return -1;
     LAUNCH(ctx, k_sd_lcp_patch, grid_for(patch.size()), BLOCK, ctx->stream,
-           (const sre_account_entry *)out, new_na, dpatch.as<uint32_t>(),
-           patch.size(), (int8_t *)ctx->d_lcp_ret2, err.as<uint32_t>());
+           out.as<sre_account_entry>(), new_na, dpatch.as<uint32_t>(),
+           patch.size(), (int8_t *)ctx->lcp_ret2.p, err.as<uint32_t>());
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
-    release_acct(ctx);
-    ctx->d_acct = (const sre_account_entry *)out;
-    ctx->na = new_na;
-    ctx->own_acct = true;
-    ctx->acct_pool_bytes = acct_bytes;
-    std::swap(ctx->d_lcp_ret, ctx->d_lcp_ret2);
-    std::swap(ctx->lcp_ret_capacity, ctx->lcp_ret2_capacity);
+    adopt_merged(ctx, out, new_na, no_st, 0);
+    std::swap(ctx->lcp_ret, ctx->lcp_ret2);
     ctx->lcp_valid = true;
     return 0;
 }
@@ -5236,11 +5159,10 @@ extern "C" int sre_root_retaining(sre_ctx *ctx, uint8_t out_root[32])
     if (begin_call(ctx, true))
         return -1;
     invalidate_retention(ctx);
-    if (grow_retained(ctx, &ctx->d_cap_rows, &ctx->cap_capacity,
-                      cap_rows_for(ctx->na), sizeof(cap_row)))
+    if (ctx->cap_rows.grow(ctx, cap_rows_for(ctx->acct.n), sizeof(cap_row)))
         return -1;
-    if (ctx->na == 0) {
-        if (ctx->ns != 0) {
+    if (ctx->acct.n == 0) {
+        if (ctx->st.n != 0) {
             set_err(ctx, "storage entries without accounts");
             return -1;
         }
@@ -5249,8 +5171,7 @@ extern "C" int sre_root_retaining(sre_ctx *ctx, uint8_t out_root[32])
         memcpy(out_root, EMPTY_ROOT_H, 32);
         return 0;
     }
-    if (grow_retained(ctx, &ctx->d_roots_ret, &ctx->roots_ret_capacity, ctx->na,
-                      32))
+    if (ctx->roots_ret.grow(ctx, ctx->acct.n, 32))
         return -1;
     DBuf err(ctx), roots(ctx), capcnt(ctx);
     if (alloc_err_flag(ctx, err))
@@ -5261,15 +5182,15 @@ extern "C" int sre_root_retaining(sre_ctx *ctx, uint8_t out_root[32])
     pass_out po;
     // full storage pass into the RETAINED roots buffer (chained deltas
     // carry and patch it instead of recomputing every segment)
-    if (run_storage_pass(ctx, (uint8_t *)ctx->d_roots_ret, &po,
+    if (run_storage_pass(ctx, (uint8_t *)ctx->roots_ret.p, &po,
                          err.as<uint32_t>()))
         return -1;
     cell_capture cap;
     cap.depth = CELL_NIBBLES;
-    cap.rows = (cap_row *)ctx->d_cap_rows;
+    cap.rows = (cap_row *)ctx->cap_rows.p;
     cap.count = capcnt.as<uint32_t>();
-    cap.capacity = ctx->cap_capacity;
-    if (run_account_pass(ctx, (const uint8_t *)ctx->d_roots_ret, 0,
+    cap.capacity = ctx->cap_rows.cap;
+    if (run_account_pass(ctx, (const uint8_t *)ctx->roots_ret.p, 0,
                          roots.as<uint8_t>(), nullptr, nullptr,
                          &po, err.as<uint32_t>(), cap))
         return -1;
@@ -5312,15 +5233,14 @@ static int incremental_root_impl(sre_ctx *ctx,
     // accounts-only states with accounts-only deltas skip the roots
     // machinery entirely (every storage root is EMPTY_ROOT; the leaf
     // kernel's null-roots path substitutes it) — the configs[4] shape
-    bool no_storage = (ctx->ns == 0 && n_st == 0);
+    bool no_storage = (ctx->st.n == 0 && n_st == 0);
     // new roots buffer: the ping-pong partner of the retained one (no
     // per-step hipMalloc at steady state), EMPTY-filled upper bound,
     // carried across the merge
-    uint64_t max_na = ctx->na + n_acct;
-    if (!no_storage && grow_retained(ctx, &ctx->d_roots_ret2,
-                                     &ctx->roots_ret2_capacity, max_na, 32))
+    uint64_t max_na = ctx->acct.n + n_acct;
+    if (!no_storage && ctx->roots_ret2.grow(ctx, max_na, 32))
         return -1;
-    void *new_roots = no_storage ? nullptr : ctx->d_roots_ret2;
+    void *new_roots = no_storage ? nullptr : ctx->roots_ret2.p;
     if (new_roots)
         LAUNCH(ctx, k_fill_empty_roots, grid_for(max_na ? max_na : 1), BLOCK,
                ctx->stream, (uint8_t *)new_roots, max_na ? max_na : 1);
@@ -5331,8 +5251,8 @@ static int incremental_root_impl(sre_ctx *ctx,
     // fix for the configs[4] shape. Everything else keeps the general
     // overlay merge.
     bool small = no_storage && n_acct > 0 && ctx->lcp_valid &&
-                 (n_acct <= (ctx->na >> 6) ||
-                  (getenv("SRE_SD_FORCE") && n_acct <= ctx->na));
+                 (n_acct <= (ctx->acct.n >> 6) ||
+                  (getenv("SRE_SD_FORCE") && n_acct <= ctx->acct.n));
     bool st_closed_form = false;
     if (small) {
         if (apply_delta_small(ctx, acct_delta, n_acct, &map))
@@ -5340,14 +5260,16 @@ static int incremental_root_impl(sre_ctx *ctx,
     } else {
         // carry only when the pre-delta state HAS storage: while ns stays 0
         // every retained root is EMPTY_ROOT (and accounts-only fast-path
-        // deltas may have drifted d_roots_ret's indexing — harmless, since
+        // deltas may have drifted roots_ret's indexing — harmless, since
         // it is then never read)
-        if (apply_delta_impl(ctx, acct_delta, n_acct, st_delta, n_st, &map,
-                             (new_roots && ctx->ns > 0)
-                                 ? (const uint8_t *)ctx->d_roots_ret
-                                 : nullptr,
-                             (uint8_t *)new_roots, &st_closed_form))
+        merge_io io;
+        io.map_out = &map;
+        if (new_roots && ctx->st.n > 0)
+            io.d_old_roots = (const uint8_t *)ctx->roots_ret.p;
+        io.d_new_roots = (uint8_t *)new_roots;
+        if (merge_delta(ctx, acct_delta, n_acct, st_delta, n_st, io))
             return -1;
+        st_closed_form = io.st_closed_form;
         ctx->lcp_valid = false; // recomputed below
     }
     // the merged state is adopted: the retained rows and storage roots
@@ -5356,7 +5278,7 @@ static int incremental_root_impl(sre_ctx *ctx,
     ctx->cells_valid = false;
     ctx->inc_cnt[3] = small;
     ctx->inc_cnt[4] = st_closed_form;
-    uint64_t na = ctx->na;
+    uint64_t na = ctx->acct.n;
     if (na == 0) {
         invalidate_retention(ctx);
         memcpy(out_root, EMPTY_ROOT_H, 32);
@@ -5369,19 +5291,14 @@ static int incremental_root_impl(sre_ctx *ctx,
         return -1;
     HIP_CHECK(ctx, bitmap.alloc(N_CELLS));
     HIP_CHECK(ctx, hipMemsetAsync(bitmap.p, 0, N_CELLS, ctx->stream));
-    HIP_CHECK(ctx, dl.alloc((n_acct ? n_acct : 1) * sizeof(sre_account_delta)));
-    if (n_acct) {
-        HIP_CHECK(ctx, hipMemcpyAsync(dl.p, acct_delta,
-                                      n_acct * sizeof(sre_account_delta),
-                                      hipMemcpyHostToDevice, ctx->stream));
+    if (to_device(ctx, dl, acct_delta, n_acct))
+        return -1;
+    if (n_acct)
         LAUNCH(ctx, k_mark_delta_cells, grid_for(n_acct), BLOCK, ctx->stream,
                dl.as<sre_account_delta>(), n_acct, bitmap.as<uint8_t>());
-    }
     if (n_st) {
-        HIP_CHECK(ctx, dls.alloc(n_st * sizeof(sre_storage_entry)));
-        HIP_CHECK(ctx, hipMemcpyAsync(dls.p, st_delta,
-                                      n_st * sizeof(sre_storage_entry),
-                                      hipMemcpyHostToDevice, ctx->stream));
+        if (to_device(ctx, dls, st_delta, n_st))
+            return -1;
         LAUNCH(ctx, k_mark_delta_cells_st, grid_for(n_st), BLOCK, ctx->stream,
                dls.as<sre_storage_entry>(), n_st, bitmap.as<uint8_t>());
     }
@@ -5393,24 +5310,19 @@ static int incremental_root_impl(sre_ctx *ctx,
         std::vector<key32> tkeys = storage_delta_accounts(st_delta, n_st);
         uint32_t nt = (uint32_t)tkeys.size();
         DBuf dtk(ctx), tlo(ctx), thi(ctx), taidx(ctx);
-        HIP_CHECK(ctx, dtk.alloc(32ull * nt));
-        HIP_CHECK(ctx, hipMemcpyAsync(dtk.p, tkeys.data(), 32ull * nt,
-                                      hipMemcpyHostToDevice, ctx->stream));
+        if (to_device(ctx, dtk, tkeys.data(), nt))
+            return -1;
         HIP_CHECK(ctx, tlo.alloc((uint64_t)nt * 4));
         HIP_CHECK(ctx, thi.alloc((uint64_t)nt * 4));
         HIP_CHECK(ctx, taidx.alloc((uint64_t)nt * 4));
         LAUNCH(ctx, k_touched_bounds, grid_for(nt), BLOCK, ctx->stream,
-               ctx->d_st, ctx->ns, ctx->d_acct, na, dtk.as<uint8_t>(), nt,
+               ctx->st.d, ctx->st.n, ctx->acct.d, na, dtk.as<uint8_t>(), nt,
                tlo.as<uint32_t>(), thi.as<uint32_t>(), taidx.as<uint32_t>(),
                (uint8_t *)new_roots, err.as<uint32_t>());
-        std::vector<uint32_t> lo(nt), hi(nt), offs(nt + 1);
-        HIP_CHECK(ctx, hipMemcpy(lo.data(), tlo.p, 4ull * nt,
-                                 hipMemcpyDeviceToHost));
-        HIP_CHECK(ctx, hipMemcpy(hi.data(), thi.p, 4ull * nt,
-                                 hipMemcpyDeviceToHost));
-        offs[0] = 0;
-        for (uint32_t t = 0; t < nt; ++t)
-            offs[t + 1] = offs[t] + (hi[t] - lo[t]);
+        std::vector<uint32_t> lo, hi;
+        if (to_host(ctx, lo, tlo, nt) || to_host(ctx, hi, thi, nt))
+            return -1;
+        std::vector<uint32_t> offs = interval_offsets(lo, hi);
         if (offs[nt] &&
             run_storage_intervals(ctx, tlo.as<uint32_t>(), thi.as<uint32_t>(),
                                   offs, (uint8_t *)new_roots, &po,
@@ -5423,13 +5335,13 @@ static int incremental_root_impl(sre_ctx *ctx,
     // it already; the general path recomputes it here (arming repair for
     // the next delta)
     if (!small) {
-        if (grow_retained(ctx, &ctx->d_lcp_ret, &ctx->lcp_ret_capacity, na + 1))
+        if (ctx->lcp_ret.grow(ctx, na + 1))
             return -1;
         LAUNCH(ctx, k_lcp_account, grid_for(na + 1), BLOCK, ctx->stream,
-               ctx->d_acct, na, 0, (int8_t *)ctx->d_lcp_ret, err.as<uint32_t>());
+               ctx->acct.d, na, 0, (int8_t *)ctx->lcp_ret.p, err.as<uint32_t>());
         ctx->lcp_valid = true;
     }
-    int8_t *lcp_p = (int8_t *)ctx->d_lcp_ret;
+    int8_t *lcp_p = (int8_t *)ctx->lcp_ret.p;
     DBuf covered(ctx);
     HIP_CHECK(ctx, recs.alloc(na * sizeof(node_rec)));
     HIP_CHECK(ctx, depths.alloc(na));
@@ -5445,7 +5357,7 @@ static int incremental_root_impl(sre_ctx *ctx,
     // seed clean cell-tops; anything invalid dirties its cell
     if (ctx->cap_count)
         LAUNCH(ctx, k_revalidate_rows, grid_for(ctx->cap_count), BLOCK,
-               ctx->stream, (const cap_row *)ctx->d_cap_rows, ctx->cap_count,
+               ctx->stream, (const cap_row *)ctx->cap_rows.p, ctx->cap_count,
                map.as<uint32_t>(), lcp_p, bitmap.as<uint8_t>(),
                recs.as<node_rec>(), depths.as<uint8_t>(), covered.as<uint8_t>(),
                hist.as<uint32_t>(),
@@ -5476,7 +5388,7 @@ static int incremental_root_impl(sre_ctx *ctx,
     }
     if (n_active)
         LAUNCH(ctx, k_leaf_account, grid_for(n_active), BLOCK, ctx->stream,
-               ctx->d_acct, na,
+               ctx->acct.d, na,
                (const uint8_t *)new_roots /* null=>EMPTY_ROOT */, lcp_p, 0,
                recs.as<node_rec>(), depths.as<uint8_t>(), hist.as<uint32_t>(),
                roots.as<uint8_t>(), nullptr, nullptr, nullptr, nullptr,
@@ -5488,11 +5400,9 @@ static int incremental_root_impl(sre_ctx *ctx,
     po.leaf_ms += ms;
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
-    if (bitmap_out) { // final dirty-cell set (incl. revalidation misses)
-        bitmap_out->resize(N_CELLS);
-        HIP_CHECK(ctx, hipMemcpy(bitmap_out->data(), bitmap.p, N_CELLS,
-                                 hipMemcpyDeviceToHost));
-    }
+    // final dirty-cell set (incl. revalidation misses)
+    if (bitmap_out && to_host(ctx, *bitmap_out, bitmap, N_CELLS))
+        return -1;
     uint32_t hist_host[66];
     HIP_CHECK(ctx, hipMemcpy(hist_host, hist.p, 66 * 4, hipMemcpyDeviceToHost));
     // every rehashed leaf (k_leaf_account) and every seeded row
@@ -5505,8 +5415,7 @@ static int incremental_root_impl(sre_ctx *ctx,
     // fresh capture for the next delta; the retained rows were consumed by
     // k_revalidate_rows above, so capturing over the same buffer is safe —
     // unless na grew past its capacity, in which case swap in a bigger one.
-    if (grow_retained(ctx, &ctx->d_cap_rows, &ctx->cap_capacity,
-                      cap_rows_for(na), sizeof(cap_row)))
+    if (ctx->cap_rows.grow(ctx, cap_rows_for(na), sizeof(cap_row)))
         return -1;
     HIP_CHECK(ctx, capcnt.alloc(4));
     HIP_CHECK(ctx, hipMemsetAsync(capcnt.p, 0, 4, ctx->stream));
@@ -5516,7 +5425,7 @@ static int incremental_root_impl(sre_ctx *ctx,
     in.recs = recs.as<node_rec>();
     in.depths = depths.as<uint8_t>();
     in.lcp = lcp_p;
-    in.keys = (const uint8_t *)ctx->d_acct + offsetof(sre_account_entry, key);
+    in.keys = (const uint8_t *)ctx->acct.d + offsetof(sre_account_entry, key);
     in.key_stride = sizeof(sre_account_entry);
     in.hist_host = hist_host;
     in.seg_roots = roots.as<uint8_t>();
@@ -5525,9 +5434,9 @@ static int incremental_root_impl(sre_ctx *ctx,
     in.bhash = with_updates ? abhash.as<uint8_t>() : nullptr;
     cell_capture cap;
     cap.depth = CELL_NIBBLES;
-    cap.rows = (cap_row *)ctx->d_cap_rows;
+    cap.rows = (cap_row *)ctx->cap_rows.p;
     cap.count = capcnt.as<uint32_t>();
-    cap.capacity = ctx->cap_capacity;
+    cap.capacity = ctx->cap_rows.cap;
     if (run_levels(ctx, in, &po, cap))
         return -1;
     if (with_updates) // account rows carry no acct_key; clear the seg stash
@@ -5540,10 +5449,8 @@ static int incremental_root_impl(sre_ctx *ctx,
     ctx->cap_count = cnt;
     ctx->inc_cnt[5] = cnt;
     // swap the ping-pong retained roots (chained deltas)
-    if (!no_storage) {
-        std::swap(ctx->d_roots_ret, ctx->d_roots_ret2);
-        std::swap(ctx->roots_ret_capacity, ctx->roots_ret2_capacity);
-    }
+    if (!no_storage)
+        std::swap(ctx->roots_ret, ctx->roots_ret2);
     ctx->cells_valid = true;
 
     HIP_CHECK(ctx, whole.stop(ctx->stream));
@@ -5683,9 +5590,10 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
     // touched storage accounts (delta, sorted)
     std::vector<key32> tkeys = storage_delta_accounts(st_delta, n_st);
 
-    if (apply_delta_impl(ctx, acct_delta, n_acct, st_delta, n_st, nullptr))
+    merge_io io;
+    if (merge_delta(ctx, acct_delta, n_acct, st_delta, n_st, io))
         return -1;
-    uint64_t na = ctx->na, ns = ctx->ns;
+    uint64_t na = ctx->acct.n, ns = ctx->st.n;
     if (na == 0) {
         if (ns != 0) {
             set_err(ctx, "storage entries without accounts");
@@ -5706,49 +5614,30 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
     if (ns) {
         // segment the resident storage; seed supplied roots / flag rebuilds
         storage_segs sg(ctx);
-        if (segment_storage(ctx, ctx->d_st, ns, err.as<uint32_t>(), sg))
+        if (segment_storage(ctx, ctx->st.d, ns, err.as<uint32_t>(), sg))
             return -1;
         const uint32_t n_seg = sg.n_seg;
         DBuf need(ctx), dkv(ctx), dtk(ctx);
         HIP_CHECK(ctx, need.alloc((uint64_t)n_seg * 4));
-        HIP_CHECK(ctx, dkv.alloc(kv.empty() ? 64 : kv.size() * 64));
-        if (!kv.empty())
-            HIP_CHECK(ctx, hipMemcpyAsync(dkv.p, kv.data(), kv.size() * 64,
-                                          hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK(ctx, dtk.alloc(tkeys.empty() ? 32 : tkeys.size() * 32));
-        if (!tkeys.empty())
-            HIP_CHECK(ctx, hipMemcpyAsync(dtk.p, tkeys.data(), tkeys.size() * 32,
-                                          hipMemcpyHostToDevice, ctx->stream));
-        LAUNCH(ctx, k_seg_need, grid_for(n_seg), BLOCK, ctx->stream, ctx->d_st,
+        if (to_device(ctx, dkv, kv.data(), kv.size()) ||
+            to_device(ctx, dtk, tkeys.data(), tkeys.size()))
+            return -1;
+        LAUNCH(ctx, k_seg_need, grid_for(n_seg), BLOCK, ctx->stream, ctx->st.d,
                sg.seg_start.as<uint32_t>(), n_seg, dkv.as<uint8_t>(),
                (uint64_t)kv.size(), dtk.as<uint8_t>(),
                (uint64_t)tkeys.size(), sg.seg_acct.as<uint32_t>(),
                acct_roots.as<uint8_t>(), need.as<uint32_t>());
-        std::vector<uint32_t> need_h(n_seg), start_h(n_seg);
-        HIP_CHECK(ctx, hipMemcpy(need_h.data(), need.p, 4ull * n_seg,
-                                 hipMemcpyDeviceToHost));
-        HIP_CHECK(ctx, hipMemcpy(start_h.data(), sg.seg_start.p, 4ull * n_seg,
-                                 hipMemcpyDeviceToHost));
-        std::vector<uint32_t> lo, hi, offs;
-        uint64_t total = 0;
-        for (uint32_t s = 0; s < n_seg; ++s)
-            if (need_h[s]) {
-                uint32_t e = s + 1 < n_seg ? start_h[s + 1] : (uint32_t)ns;
-                lo.push_back(start_h[s]);
-                hi.push_back(e);
-                offs.push_back((uint32_t)total);
-                total += e - start_h[s];
-            }
-        offs.push_back((uint32_t)total);
-        if (total) {
-            uint32_t nneed = (uint32_t)lo.size();
+        std::vector<uint32_t> need_h, start_h, lo, hi;
+        if (to_host(ctx, need_h, need, n_seg) ||
+            to_host(ctx, start_h, sg.seg_start, n_seg))
+            return -1;
+        needed_intervals(need_h, start_h, ns, lo, hi);
+        std::vector<uint32_t> offs = interval_offsets(lo, hi);
+        if (offs.back()) {
             DBuf dlo(ctx), dhi(ctx);
-            HIP_CHECK(ctx, dlo.alloc(4ull * nneed));
-            HIP_CHECK(ctx, dhi.alloc(4ull * nneed));
-            HIP_CHECK(ctx, hipMemcpyAsync(dlo.p, lo.data(), 4ull * nneed,
-                                          hipMemcpyHostToDevice, ctx->stream));
-            HIP_CHECK(ctx, hipMemcpyAsync(dhi.p, hi.data(), 4ull * nneed,
-                                          hipMemcpyHostToDevice, ctx->stream));
+            if (to_device(ctx, dlo, lo.data(), lo.size()) ||
+                to_device(ctx, dhi, hi.data(), hi.size()))
+                return -1;
             if (run_storage_intervals(ctx, dlo.as<uint32_t>(),
                                       dhi.as<uint32_t>(), offs,
                                       acct_roots.as<uint8_t>(), &po,
@@ -6254,28 +6143,6 @@ static int hs_resolve_ties(sre_ctx *ctx, hs_pairs &pr, uint64_t n, const uint8_t
     return 0;
 }
 
-// A pool buffer that becomes a resident array on success and goes back to
-// the pool otherwise.
-struct hs_out {
-    sre_ctx *ctx;
-    size_t bytes = 0;
-    void *p = nullptr;
-    explicit hs_out(sre_ctx *c) : ctx(c) {}
-    ~hs_out() { pool_put(ctx, bytes, p); }
-    bool alloc(size_t b)
-    {
-        bytes = b;
-        p = pool_get(ctx, b);
-        return p != nullptr;
-    }
-    void *take()
-    {
-        void *q = p;
-        p = nullptr;
-        return q;
-    }
-};
-
 static int plain_state_device(sre_ctx *ctx, const uint8_t *d_pa, uint64_t na,
                               const uint8_t *d_ps, uint64_t ns)
 {
@@ -6296,14 +6163,14 @@ static int plain_state_device(sre_ctx *ctx, const uint8_t *d_pa, uint64_t na,
     uint32_t *d_err = err.as<uint32_t>();
 
     // Build into temporaries; the resident state is touched only at the end.
-    hs_out new_acct(ctx), new_st(ctx);
-    if (!new_acct.alloc((na ? na : 1) * sizeof(sre_account_entry)) ||
-        !new_st.alloc((ns ? ns : 1) * sizeof(sre_storage_entry))) {
+    DBuf new_acct(ctx), new_st(ctx);
+    if (new_acct.alloc((na ? na : 1) * sizeof(sre_account_entry)) != hipSuccess ||
+        new_st.alloc((ns ? ns : 1) * sizeof(sre_storage_entry)) != hipSuccess) {
         set_err(ctx, "plain state: out of memory (sorted rows)");
         return -1;
     }
-    sre_account_entry *acct = (sre_account_entry *)new_acct.p;
-    sre_storage_entry *st = (sre_storage_entry *)new_st.p;
+    sre_account_entry *acct = new_acct.as<sre_account_entry>();
+    sre_storage_entry *st = new_st.as<sre_storage_entry>();
 
     if (na) {
         DBuf hk(ctx);
@@ -6342,16 +6209,8 @@ static int plain_state_device(sre_ctx *ctx, const uint8_t *d_pa, uint64_t na,
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
 
     invalidate_retention(ctx);
-    release_acct(ctx);
-    ctx->acct_pool_bytes = new_acct.bytes;
-    ctx->d_acct = (const sre_account_entry *)new_acct.take();
-    ctx->na = na;
-    ctx->own_acct = true;
-    release_st(ctx);
-    ctx->st_pool_bytes = new_st.bytes;
-    ctx->d_st = (const sre_storage_entry *)new_st.take();
-    ctx->ns = ns;
-    ctx->own_st = true;
+    ctx->acct.adopt(ctx, new_acct, na);
+    ctx->st.adopt(ctx, new_st, ns);
     memcpy(ctx->hs_cnt, cnt, sizeof(cnt));
     return 0;
 }
@@ -6390,8 +6249,8 @@ extern "C" int sre_upload_plain_state(sre_ctx *ctx, const sre_plain_account *acc
 
 extern "C" int sre_resident_counts(sre_ctx *ctx, uint64_t *na, uint64_t *ns)
 {
-    *na = ctx->na;
-    *ns = ctx->ns;
+    *na = ctx->acct.n;
+    *ns = ctx->st.n;
     return 0;
 }
 
@@ -6413,13 +6272,13 @@ static int download_rows(sre_ctx *ctx, const char *what, const void *d, uint64_t
 
 extern "C" int sre_download_accounts(sre_ctx *ctx, sre_account_entry *out, uint64_t n)
 {
-    return download_rows(ctx, "sre_download_accounts", ctx->d_acct, ctx->na,
+    return download_rows(ctx, "sre_download_accounts", ctx->acct.d, ctx->acct.n,
                          sizeof(sre_account_entry), out, n);
 }
 
 extern "C" int sre_download_storage(sre_ctx *ctx, sre_storage_entry *out, uint64_t n)
 {
-    return download_rows(ctx, "sre_download_storage", ctx->d_st, ctx->ns,
+    return download_rows(ctx, "sre_download_storage", ctx->st.d, ctx->st.n,
                          sizeof(sre_storage_entry), out, n);
 }
 
