@@ -80,6 +80,13 @@
  *     retention disarmed: the next incremental call fails with
  *     `needs sre_root_retaining first` instead of computing from records
  *     of the previous state.
+ *   - The stored revert (revert capture, below) follows the same line. A
+ *     call rejected for its inputs leaves it exactly as it was: rows,
+ *     counts and the revert counters; a wrong n at sre_revert_get and an
+ *     unwind without armed retention are such rejections. A call that
+ *     fails AFTER adoption keeps the NEW revert, the one of the delta that
+ *     is now resident: a fresh sre_root_retaining followed by applying it
+ *     still gets the previous state back.
  */
 #ifndef SRE_H
 #define SRE_H
@@ -470,6 +477,79 @@ int sre_download_storage(sre_ctx *ctx, sre_storage_entry *out, uint64_t n);
  * cannot show that the tie path or the pass skipping ran (test gate
  * SRE_HS_KEY_BITS). */
 int sre_get_hash_sort_counters(sre_ctx *ctx, uint64_t out[6]);
+
+/* ---- revert capture and unwind ------------------------------------------
+ *
+ * The way back from a delta. MerkleStage::Unwind
+ * (crates/stages/stages/src/stages/merkle.rs:79-108, the recomputation at
+ * merkle.rs:626) builds the reverted HashedPostState from the account and
+ * storage changesets (DatabaseHashedPostState::from_reverts,
+ * crates/trie/db/src/state.rs:143-150; prefix sets from the changesets,
+ * crates/trie/db/src/prefix_set.rs) and runs incremental_root_with_updates
+ * (crates/trie/db/src/state.rs:62) over it; the pipeline does so whenever a
+ * computed root does not match the header (merkle.rs:457-474). The engine
+ * holds every row such a revert needs, sorted, at the moment it merges a
+ * delta: with capture on it keeps them.
+ *
+ * The revert of a valid delta (rows, strows) over the resident state `pre`
+ * is itself a valid delta in the same row formats; applied to the
+ * post-delta state it reproduces `pre` row for row.
+ *   Account rows, one decision per delta account row, in delta order:
+ *   - key resident in `pre` (upserted or destroyed): the old account row,
+ *     deleted = 0;
+ *   - key not resident, upserted: a row with deleted = 1, nonce and balance
+ *     zero, code_hash KECCAK_EMPTY;
+ *   - key not resident, deleted = 1: a no-op forward, no row.
+ *   Storage rows, sorted by (acct_key, slot_key):
+ *   - a delta row whose account this delta inserts (its revert destroys
+ *     the account, storage included) or whose account is not resident at
+ *     all (a no-op deletion): no row;
+ *   - slot resident in `pre`: (acct, slot, old value);
+ *   - slot not resident, forward value nonzero: (acct, slot, 0);
+ *   - slot not resident, forward value zero: no row;
+ *   - for every resident account the delta destroys: ALL its resident rows.
+ *
+ * sre_set_revert_capture turns capture on or off (off at creation). While
+ * on, each successful sre_apply_delta, sre_incremental_root,
+ * sre_incremental_root_with_updates and sre_root_from_nodes computes the
+ * revert of its delta on the device before the merge and stores it, device-
+ * resident, at the point where the merged arrays become the resident state.
+ * Only the LAST revert is kept; to unwind several blocks, fetch each with
+ * sre_revert_get and apply them newest first through the incremental calls
+ * (the changeset range of merkle.rs:626, one block at a time). Any upload,
+ * a borrowed array, a plain-state upload that installs a state, and turning
+ * capture off drop the stored revert (counts 0, buffers released);
+ * sre_destroy releases it. With capture off nothing is computed and nothing
+ * is allocated. For failed calls see "Failed calls" above.
+ *
+ * sre_revert_counts reports the stored revert's row counts, (0, 0) when
+ * none is stored; sre_revert_get copies it out, and n_acct and n_st must
+ * equal those counts (anything else is an argument error). */
+int sre_set_revert_capture(sre_ctx *ctx, int on);
+int sre_revert_counts(sre_ctx *ctx, uint64_t *n_acct, uint64_t *n_st);
+int sre_revert_get(sre_ctx *ctx, sre_account_delta *acct, uint64_t n_acct,
+                   sre_storage_entry *st, uint64_t n_st);
+
+/* Unwind in one call: sre_unwind is sre_incremental_root, and
+ * sre_unwind_with_updates is sre_incremental_root_with_updates — the call
+ * MerkleStage::Unwind makes — handed the stored revert. Retention
+ * requirements, entry behaviour and messages are those of the call each
+ * stands for. With nothing stored both fail with a message containing
+ * `no-revert-captured` and change nothing. With capture on the unwind
+ * captures too, so afterwards the stored revert is the redo. The rows reach
+ * the merge through a host copy (the merges plan on the host). */
+int sre_unwind(sre_ctx *ctx, uint8_t out_root[32]);
+int sre_unwind_with_updates(sre_ctx *ctx, uint8_t out_root[32]);
+
+/* Read-only: what the last capture that was stored did (all zero when no
+ * revert is stored):
+ *   out[0] account rows emitted
+ *   out[1] storage rows emitted from delta rows
+ *   out[2] storage rows copied out of destroyed accounts' segments
+ *   out[3] delta rows, account and storage, that produced no row
+ * Exists for the reason sre_get_path_counters does: tests use it to show
+ * which branch of the definition ran. */
+int sre_get_revert_counters(sre_ctx *ctx, uint64_t out[4]);
 
 #ifdef __cplusplus
 }

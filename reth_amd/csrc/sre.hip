@@ -52,6 +52,7 @@
 #include "merge_plan.h" // the E_* bit numbers live there
 #include "proof_host.h"
 #include "radix.h"
+#include "revert_plan.h"
 #include "updates_diff.h"
 
 #define BLOCK 256u
@@ -2685,6 +2686,209 @@ __global__ void k_sds_wipes(const sre_storage_entry *__restrict__ base,
     whi[a] = (uint32_t)lo2;
 }
 
+// ---- revert capture (sre_set_revert_capture) --------------
+// One pass over the DELTA rows, before any merge and whichever merge runs
+// afterwards: what every delta row overwrites or removes is read out of the
+// resident arrays into a delta that undoes it. Row decisions and output
+// positions: revert_plan.h. Runs on unvalidated storage rows (the merges
+// validate), so every index below is bounded for any input; the account
+// delta's order is checked by the host before the pass starts.
+
+__constant__ uint8_t D_KECCAK_EMPTY[32] = {
+    0xc5, 0xd2, 0x46, 0x01, 0x86, 0xf7, 0x23, 0x3c, 0x92, 0x7e, 0x7d, 0xb2,
+    0xdc, 0xc7, 0x03, 0xc0, 0xe5, 0x00, 0xb6, 0x53, 0xca, 0x82, 0x27, 0x3b,
+    0x7b, 0xfa, 0xd8, 0x04, 0x5d, 0x85, 0xa4, 0x70};
+
+// account delta row k: its decision, the resident row it reads, and the
+// resident storage segment [seglo, seglo + seglen) it wipes (as k_sds_wipes)
+__global__ void k_rv_acct(const sre_account_entry *__restrict__ acct, uint64_t na,
+                          const sre_storage_entry *__restrict__ st, uint64_t ns,
+                          const sre_account_delta *__restrict__ dl, uint64_t nd,
+                          uint32_t *__restrict__ kind, /* nd */
+                          uint32_t *__restrict__ flag, /* nd + 1 */
+                          uint32_t *__restrict__ src,  /* nd */
+                          uint32_t *__restrict__ seglo,
+                          uint32_t *__restrict__ seglen /* nd + 1 */)
+{
+    uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > nd)
+        return;
+    if (k == nd) { // scan sentinels
+        flag[k] = 0;
+        seglen[k] = 0;
+        return;
+    }
+    const uint8_t *key = dl[k].key;
+    uint64_t p = lb_keys((const uint8_t *)acct, sizeof(sre_account_entry), na,
+                         key, 32);
+    bool resident = p < na && cmp_key32(acct[p].key, key) == 0;
+    bool deleted = dl[k].deleted != 0;
+    uint32_t kd = rv_acct_row(resident, deleted);
+    kind[k] = kd;
+    flag[k] = kd != RV_NONE;
+    src[k] = (uint32_t)p;
+    uint64_t lo = 0, lo2 = 0;
+    if (resident && deleted) {
+        uint64_t hi = ns;
+        while (lo < hi) { // first i with acct_key >= key
+            uint64_t mid = (lo + hi) / 2;
+            if (cmp_key32(st[mid].acct_key, key) < 0)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        lo2 = lo;
+        hi = ns;
+        while (lo2 < hi) { // first i with acct_key > key
+            uint64_t mid = (lo2 + hi) / 2;
+            if (cmp_key32(st[mid].acct_key, key) <= 0)
+                lo2 = mid + 1;
+            else
+                hi = mid;
+        }
+    }
+    seglo[k] = (uint32_t)lo;
+    seglen[k] = (uint32_t)(lo2 - lo);
+}
+
+// storage delta row j: its decision, the resident row it reads, and the
+// lower bound of its account among the account delta keys (the owner
+// lookup of st_row_orphan, kept for the position formula)
+__global__ void k_rv_st(const sre_storage_entry *__restrict__ st, uint64_t ns,
+                        const sre_account_entry *__restrict__ acct, uint64_t na,
+                        const sre_account_delta *__restrict__ dl_a, uint64_t n_acct,
+                        const sre_storage_entry *__restrict__ dl, uint64_t nd,
+                        uint32_t *__restrict__ kind, /* nd */
+                        uint32_t *__restrict__ flag, /* nd + 1 */
+                        uint32_t *__restrict__ src,  /* nd */
+                        uint32_t *__restrict__ owner /* nd */)
+{
+    uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > nd)
+        return;
+    if (j == nd) {
+        flag[j] = 0;
+        return;
+    }
+    const uint8_t *akey = dl[j].acct_key;
+    uint64_t q = lb_keys((const uint8_t *)dl_a, sizeof(sre_account_delta),
+                         n_acct, akey, 32);
+    bool destroyed = q < n_acct && cmp_key32(dl_a[q].key, akey) == 0 &&
+                     dl_a[q].deleted != 0;
+    uint64_t a = lb_keys((const uint8_t *)acct, sizeof(sre_account_entry), na,
+                         akey, 32);
+    bool owner_resident = a < na && cmp_key32(acct[a].key, akey) == 0;
+    uint64_t p = lb_keys((const uint8_t *)st, sizeof(sre_storage_entry), ns,
+                         (const uint8_t *)&dl[j], 64);
+    bool slot_resident = p < ns && cmp_key64((const uint8_t *)&st[p],
+                                             (const uint8_t *)&dl[j]) == 0;
+    uint32_t kd = rv_st_row(owner_resident, destroyed, slot_resident,
+                            min_be_len(dl[j].value) != 0);
+    kind[j] = kd;
+    flag[j] = kd != RV_NONE;
+    src[j] = (uint32_t)p;
+    owner[j] = (uint32_t)q;
+}
+
+// emitted account rows, compacted in delta order
+__global__ void k_rv_emit_acct(const sre_account_entry *__restrict__ acct,
+                               const sre_account_delta *__restrict__ dl,
+                               uint64_t nd, const uint32_t *__restrict__ kind,
+                               const uint32_t *__restrict__ ea,
+                               const uint32_t *__restrict__ src,
+                               sre_account_delta *__restrict__ out)
+{
+    uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nd || kind[k] == RV_NONE)
+        return;
+    sre_account_delta r;
+    memset(&r, 0, sizeof(r));
+    memcpy(r.key, dl[k].key, 32);
+    if (kind[k] == RV_OLD) {
+        const sre_account_entry *o = &acct[src[k]];
+        r.nonce = o->nonce;
+        memcpy(r.balance, o->balance, 32);
+        memcpy(r.code_hash, o->code_hash, 32);
+    } else {
+        for (int b = 0; b < 32; ++b)
+            r.code_hash[b] = D_KECCAK_EMPTY[b];
+        r.deleted = 1;
+    }
+    out[ea[k]] = r;
+}
+
+// emitted storage delta rows, at rv_delta_row_pos
+__global__ void k_rv_emit_st(const sre_storage_entry *__restrict__ st,
+                             const sre_storage_entry *__restrict__ dl,
+                             uint64_t nd, const uint32_t *__restrict__ kind,
+                             const uint32_t *__restrict__ es,
+                             const uint32_t *__restrict__ src,
+                             const uint32_t *__restrict__ owner,
+                             const uint32_t *__restrict__ segsum,
+                             sre_storage_entry *__restrict__ out)
+{
+    uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nd || kind[j] == RV_NONE)
+        return;
+    const uint64_t *s = (const uint64_t *)&dl[j];
+    uint64_t *d = (uint64_t *)&out[rv_delta_row_pos(es, j, segsum, owner[j])];
+#pragma unroll
+    for (int w = 0; w < 8; ++w) // (acct_key, slot_key)
+        d[w] = s[w];
+    uint64_t v[4] = {0, 0, 0, 0}; // RV_GONE: a zero value deletes the slot
+    if (kind[j] == RV_OLD) {
+        const uint64_t *o = (const uint64_t *)st[src[j]].value;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+            v[w] = o[w];
+    }
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+        d[8 + w] = v[w];
+}
+
+// per account delta row: emitted storage delta rows with a smaller account
+// key (the second term of rv_segment_row_pos)
+__global__ void k_rv_seg_base(const sre_account_delta *__restrict__ dl_a,
+                              uint64_t n_acct,
+                              const uint32_t *__restrict__ seglen,
+                              const sre_storage_entry *__restrict__ dl,
+                              uint64_t nd, uint32_t *__restrict__ segp)
+{
+    uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_acct)
+        return;
+    segp[k] = seglen[k] ? (uint32_t)lb_keys((const uint8_t *)dl,
+                                            sizeof(sre_storage_entry), nd,
+                                            dl_a[k].key, 32)
+                        : 0u;
+}
+
+// The destroyed accounts' resident rows, flat over ALL wiped rows (segment
+// sizes are as skewed as contract storage; a pass per segment would run as
+// long as its largest one). V = uint4: six lanes move one 96-byte row as
+// 16-byte loads and stores; V = uint64_t (twelve lanes) serves a borrowed
+// storage array that is only 8-byte aligned.
+template <typename V>
+__global__ void k_rv_copy_segs(const sre_storage_entry *__restrict__ st,
+                               const uint32_t *__restrict__ segsum,
+                               const uint32_t *__restrict__ seglo,
+                               const uint32_t *__restrict__ segp,
+                               uint64_t nseg, uint64_t wiped,
+                               const uint32_t *__restrict__ es,
+                               sre_storage_entry *__restrict__ out)
+{
+    constexpr uint64_t LANES = sizeof(sre_storage_entry) / sizeof(V);
+    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t w = t / LANES, part = t % LANES;
+    if (w >= wiped)
+        return;
+    uint64_t k = rv_segment_of(segsum, nseg, w);
+    uint64_t from = seglo[k] + (w - segsum[k]);
+    uint64_t to = rv_segment_row_pos(w, es, segp[k]);
+    ((V *)&out[to])[part] = ((const V *)&st[from])[part];
+}
+
 // wipes_before / merged_pos: merge_plan.h
 __global__ void k_sds_scatter(const sre_storage_entry *__restrict__ base,
                               uint64_t ns,
@@ -3221,6 +3425,14 @@ struct sre_ctx {
     // deltas patch O(delta) boundary lcps instead of recomputing all na
     retained_buf lcp_ret, lcp_ret2;
     bool lcp_valid = false; // lcp_ret matches the resident accounts
+    // revert capture (sre_set_revert_capture): the revert of the LAST
+    // adopted delta, device-resident in pool buffers, and what its capture
+    // did (sre_get_revert_counters). Nothing is held while rv_have is false.
+    bool rv_on = false;
+    bool rv_have = false;
+    resident<sre_account_delta> rv_acct;
+    resident<sre_storage_entry> rv_st;
+    uint64_t rv_cnt[4] = {0, 0, 0, 0};
     // size-class buffer pool: the level machinery allocates/frees dozens of
     // transient arrays per level; hipMalloc latency would dominate small
     // jobs. Freed buffers are cached by power-of-2 class and reused (also
@@ -3284,6 +3496,8 @@ static void pool_put(sre_ctx *ctx, size_t bytes, void *p)
 
 static std::string g_err;
 
+static void clear_revert(sre_ctx *ctx);
+
 static void set_err(sre_ctx *ctx, const std::string &msg)
 {
     if (ctx)
@@ -3327,6 +3541,7 @@ extern "C" void sre_destroy(sre_ctx *ctx)
         return;
     ctx->acct.release(ctx);
     ctx->st.release(ctx);
+    clear_revert(ctx);
     for (retained_buf *b : {&ctx->cap_rows, &ctx->roots_ret, &ctx->roots_ret2,
                             &ctx->lcp_ret, &ctx->lcp_ret2})
         if (b->p)
@@ -3381,6 +3596,7 @@ int resident<T>::upload(sre_ctx *ctx, const T *entries, uint64_t count)
     if (check_cap(ctx, count))
         return -1;
     invalidate_retention(ctx);
+    clear_revert(ctx);
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
     release(ctx);
     void *p = nullptr;
@@ -3401,6 +3617,7 @@ int resident<T>::borrow(sre_ctx *ctx, const void *d_entries, uint64_t count)
     if (check_cap(ctx, count))
         return -1;
     invalidate_retention(ctx);
+    clear_revert(ctx);
     release(ctx);
     d = (const T *)d_entries;
     n = count;
@@ -3531,6 +3748,16 @@ template <typename T> void resident<T>::adopt(sre_ctx *ctx, DBuf &buf, uint64_t 
     d = (const T *)buf.take();
     n = count;
     own = true;
+}
+
+// Drop the stored revert: counts 0, buffers back to the pool.
+static void clear_revert(sre_ctx *ctx)
+{
+    ctx->rv_acct.release(ctx);
+    ctx->rv_st.release(ctx);
+    ctx->rv_acct.n = ctx->rv_st.n = 0;
+    ctx->rv_have = false;
+    memset(ctx->rv_cnt, 0, sizeof(ctx->rv_cnt));
 }
 
 // Owning HIP event. A failed create leaves a null event, which the first
@@ -4883,11 +5110,114 @@ static int alloc_merged(sre_ctx *ctx, DBuf &out, uint64_t n, size_t row_bytes,
     return 0;
 }
 
-// Tail of every delta merge: the merged arrays become the resident state.
+// The revert of the delta being merged, in temporaries until adopt_merged
+// installs it (a rejected delta leaves the stored revert alone).
+struct revert_tmp {
+    sre_ctx *ctx;
+    DBuf acct{ctx}, st{ctx};
+    uint64_t na = 0, ns = 0;
+    uint64_t cnt[4] = {0, 0, 0, 0};
+    bool valid = false;
+};
+
+// Revert capture: read out of the resident arrays, before they are merged,
+// the delta that undoes (dl_a, dl_s) — DESIGN.md §15, revert_plan.h. The
+// same pass serves every merge path. The storage rows are not validated
+// yet (the merges do that; on rejection rv is dropped): every index is
+// bounded for any storage input. An unsorted account delta would let
+// destroyed segments repeat and their u32 prefix sums wrap, so the host
+// checks its order first and skips the pass; the merge then rejects.
+static int capture_revert(sre_ctx *ctx, const sre_account_delta *acct_delta,
+                          const sre_account_delta *dl_a, uint64_t n_acct,
+                          const sre_storage_entry *dl_s, uint64_t n_st,
+                          revert_tmp &rv)
+{
+    if (acct_delta_order(acct_delta, n_acct))
+        return 0;
+    uint64_t na = ctx->acct.n, ns = ctx->st.n;
+    DBuf ka(ctx), fa(ctx), ea(ctx), sa(ctx), seglo(ctx), seglen(ctx), segsum(ctx),
+        segp(ctx), ks(ctx), fs(ctx), es(ctx), ss(ctx), owner(ctx);
+    HIP_CHECK(ctx, ka.alloc(n_acct * 4));
+    HIP_CHECK(ctx, fa.alloc((n_acct + 1) * 4));
+    HIP_CHECK(ctx, ea.alloc((n_acct + 1) * 4));
+    HIP_CHECK(ctx, sa.alloc(n_acct * 4));
+    HIP_CHECK(ctx, seglo.alloc(n_acct * 4));
+    HIP_CHECK(ctx, seglen.alloc((n_acct + 1) * 4));
+    HIP_CHECK(ctx, segsum.alloc((n_acct + 1) * 4));
+    HIP_CHECK(ctx, segp.alloc(n_acct * 4));
+    HIP_CHECK(ctx, ks.alloc(n_st * 4));
+    HIP_CHECK(ctx, fs.alloc((n_st + 1) * 4));
+    HIP_CHECK(ctx, es.alloc((n_st + 1) * 4));
+    HIP_CHECK(ctx, ss.alloc(n_st * 4));
+    HIP_CHECK(ctx, owner.alloc(n_st * 4));
+    LAUNCH(ctx, k_rv_acct, grid_for(n_acct + 1), BLOCK, ctx->stream, ctx->acct.d,
+           na, ctx->st.d, ns, dl_a, n_acct, ka.as<uint32_t>(), fa.as<uint32_t>(),
+           sa.as<uint32_t>(), seglo.as<uint32_t>(), seglen.as<uint32_t>());
+    LAUNCH(ctx, k_rv_st, grid_for(n_st + 1), BLOCK, ctx->stream, ctx->st.d, ns,
+           ctx->acct.d, na, dl_a, n_acct, dl_s, n_st, ks.as<uint32_t>(),
+           fs.as<uint32_t>(), ss.as<uint32_t>(), owner.as<uint32_t>());
+    uint32_t ta = 0, ts = 0, wiped = 0;
+    if (scan_u32(ctx, fa.as<uint32_t>(), ea.as<uint32_t>(), n_acct + 1, &ta) ||
+        scan_u32(ctx, seglen.as<uint32_t>(), segsum.as<uint32_t>(), n_acct + 1,
+                 &wiped) ||
+        scan_u32(ctx, fs.as<uint32_t>(), es.as<uint32_t>(), n_st + 1, &ts))
+        return -1;
+    rv.na = ta;
+    rv.ns = (uint64_t)ts + wiped;
+    if (rv.acct.alloc(rv.na * sizeof(sre_account_delta)) != hipSuccess ||
+        rv.st.alloc(rv.ns * sizeof(sre_storage_entry)) != hipSuccess) {
+        set_err(ctx, "revert capture: out of memory");
+        return -1;
+    }
+    if (ta)
+        LAUNCH(ctx, k_rv_emit_acct, grid_for(n_acct), BLOCK, ctx->stream,
+               ctx->acct.d, dl_a, n_acct, ka.as<uint32_t>(), ea.as<uint32_t>(),
+               sa.as<uint32_t>(), rv.acct.as<sre_account_delta>());
+    if (ts)
+        LAUNCH(ctx, k_rv_emit_st, grid_for(n_st), BLOCK, ctx->stream, ctx->st.d,
+               dl_s, n_st, ks.as<uint32_t>(), es.as<uint32_t>(),
+               ss.as<uint32_t>(), owner.as<uint32_t>(), segsum.as<uint32_t>(),
+               rv.st.as<sre_storage_entry>());
+    if (wiped) {
+        LAUNCH(ctx, k_rv_seg_base, grid_for(n_acct), BLOCK, ctx->stream, dl_a,
+               n_acct, seglen.as<uint32_t>(), dl_s, n_st, segp.as<uint32_t>());
+        bool wide = ((uintptr_t)ctx->st.d & 15) == 0;
+        uint64_t lanes = sizeof(sre_storage_entry) / (wide ? 16 : 8);
+        if (wide)
+            LAUNCH(ctx, k_rv_copy_segs<uint4>, grid_for(wiped * lanes), BLOCK,
+                   ctx->stream, ctx->st.d, segsum.as<uint32_t>(),
+                   seglo.as<uint32_t>(), segp.as<uint32_t>(), n_acct,
+                   (uint64_t)wiped, es.as<uint32_t>(),
+                   rv.st.as<sre_storage_entry>());
+        else
+            LAUNCH(ctx, k_rv_copy_segs<uint64_t>, grid_for(wiped * lanes), BLOCK,
+                   ctx->stream, ctx->st.d, segsum.as<uint32_t>(),
+                   seglo.as<uint32_t>(), segp.as<uint32_t>(), n_acct,
+                   (uint64_t)wiped, es.as<uint32_t>(),
+                   rv.st.as<sre_storage_entry>());
+    }
+    // the index arrays above go back to the pool when this returns
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    rv.cnt[0] = ta;
+    rv.cnt[1] = ts;
+    rv.cnt[2] = wiped;
+    rv.cnt[3] = (n_acct - ta) + (n_st - ts);
+    rv.valid = true;
+    return 0;
+}
+
+// Tail of every delta merge: the merged arrays become the resident state,
+// and the captured revert (if any) the stored one.
 // An empty st means the storage array was not merged and stays in place.
 static void adopt_merged(sre_ctx *ctx, DBuf &acct, uint64_t na, DBuf &st,
-                         uint64_t ns)
+                         uint64_t ns, revert_tmp &rv)
 {
+    if (rv.valid) {
+        ctx->rv_acct.adopt(ctx, rv.acct, rv.na);
+        ctx->rv_st.adopt(ctx, rv.st, rv.ns);
+        memcpy(ctx->rv_cnt, rv.cnt, sizeof(rv.cnt));
+        ctx->rv_have = true;
+    }
     const size_t adopted[2] = {acct.sz, st.p ? st.sz : 0};
     ctx->acct.adopt(ctx, acct, na);
     if (st.p)
@@ -5051,7 +5381,14 @@ static int merge_delta(sre_ctx *ctx, const sre_account_delta *acct_delta,
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
     delta_merge m{ctx, acct_delta, n_acct, st_delta, n_st};
     if (alloc_err_flag(ctx, m.err) || to_device(ctx, m.dl_a, acct_delta, n_acct) ||
-        to_device(ctx, m.dl_s, st_delta, n_st) || merge_accounts_general(m, io))
+        to_device(ctx, m.dl_s, st_delta, n_st))
+        return -1;
+    revert_tmp rv{ctx};
+    if (ctx->rv_on &&
+        capture_revert(ctx, acct_delta, m.dl_a.as<sre_account_delta>(), n_acct,
+                       m.dl_s.as<sre_storage_entry>(), n_st, rv))
+        return -1;
+    if (merge_accounts_general(m, io))
         return -1;
     uint64_t ns = ctx->st.n;
     if (ns && n_st == 0 && m.n_del == 0 && ctx->st.own) {
@@ -5066,7 +5403,7 @@ static int merge_delta(sre_ctx *ctx, const sre_account_delta *acct_delta,
     } else if (merge_storage_general(m)) {
         return -1;
     }
-    adopt_merged(ctx, m.new_acct, m.new_na, m.new_st, m.new_ns);
+    adopt_merged(ctx, m.new_acct, m.new_na, m.new_st, m.new_ns, rv);
     return 0;
 }
 
@@ -5096,6 +5433,10 @@ static int apply_delta_small(sre_ctx *ctx, const sre_account_delta *acct_delta,
     DBuf dl(ctx), bpos(ctx), match(ctx), mex(ctx), eex(ctx), npos(ctx),
         dpatch(ctx), err(ctx), out(ctx), no_st(ctx);
     if (to_device(ctx, dl, acct_delta, nd))
+        return -1;
+    revert_tmp rv{ctx};
+    if (ctx->rv_on && capture_revert(ctx, acct_delta, dl.as<sre_account_delta>(),
+                                     nd, nullptr, 0, rv))
         return -1;
     HIP_CHECK(ctx, bpos.alloc(nd * 4));
     HIP_CHECK(ctx, match.alloc(nd * 4));
@@ -5140,7 +5481,7 @@ static int apply_delta_small(sre_ctx *ctx, const sre_account_delta *acct_delta,
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (check_err(ctx, err.as<uint32_t>()))
         return -1;
-    adopt_merged(ctx, out, new_na, no_st, 0);
+    adopt_merged(ctx, out, new_na, no_st, 0, rv);
     std::swap(ctx->lcp_ret, ctx->lcp_ret2);
     ctx->lcp_valid = true;
     return 0;
@@ -6209,6 +6550,7 @@ static int plain_state_device(sre_ctx *ctx, const uint8_t *d_pa, uint64_t na,
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
 
     invalidate_retention(ctx);
+    clear_revert(ctx);
     ctx->acct.adopt(ctx, new_acct, na);
     ctx->st.adopt(ctx, new_st, ns);
     memcpy(ctx->hs_cnt, cnt, sizeof(cnt));
@@ -6285,5 +6627,87 @@ extern "C" int sre_download_storage(sre_ctx *ctx, sre_storage_entry *out, uint64
 extern "C" int sre_get_hash_sort_counters(sre_ctx *ctx, uint64_t out[6])
 {
     memcpy(out, ctx->hs_cnt, sizeof(ctx->hs_cnt));
+    return 0;
+}
+
+// ---- revert capture and unwind (include/sre.h) ----------------------------
+
+extern "C" int sre_set_revert_capture(sre_ctx *ctx, int on)
+{
+    ctx->rv_on = on != 0;
+    if (!ctx->rv_on)
+        clear_revert(ctx);
+    return 0;
+}
+
+extern "C" int sre_revert_counts(sre_ctx *ctx, uint64_t *n_acct, uint64_t *n_st)
+{
+    *n_acct = ctx->rv_have ? ctx->rv_acct.n : 0;
+    *n_st = ctx->rv_have ? ctx->rv_st.n : 0;
+    return 0;
+}
+
+extern "C" int sre_revert_get(sre_ctx *ctx, sre_account_delta *acct, uint64_t n_acct,
+                              sre_storage_entry *st, uint64_t n_st)
+{
+    uint64_t ha = ctx->rv_have ? ctx->rv_acct.n : 0;
+    uint64_t hs = ctx->rv_have ? ctx->rv_st.n : 0;
+    if (n_acct != ha || n_st != hs) {
+        set_err(ctx, "sre_revert_get: n = (" + std::to_string(n_acct) + ", " +
+                         std::to_string(n_st) + ") but the stored revert has (" +
+                         std::to_string(ha) + ", " + std::to_string(hs) + ") rows");
+        return -1;
+    }
+    HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ha)
+        HIP_CHECK(ctx, hipMemcpy(acct, ctx->rv_acct.d, ha * sizeof(sre_account_delta),
+                                 hipMemcpyDeviceToHost));
+    if (hs)
+        HIP_CHECK(ctx, hipMemcpy(st, ctx->rv_st.d, hs * sizeof(sre_storage_entry),
+                                 hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The stored revert as host rows: the merges take host pointers and plan on
+// the host, and the copies outlive the stored revert, which the unwind
+// overwrites with the redo when capture is on.
+static int unwind_rows(sre_ctx *ctx, const char *who,
+                       std::vector<sre_account_delta> &acct,
+                       std::vector<sre_storage_entry> &st)
+{
+    if (!ctx->rv_have) {
+        set_err(ctx, std::string(who) + ": no-revert-captured (turn capture on "
+                                        "before the delta to unwind)");
+        return -1;
+    }
+    acct.resize(ctx->rv_acct.n);
+    st.resize(ctx->rv_st.n);
+    return sre_revert_get(ctx, acct.data(), acct.size(), st.data(), st.size());
+}
+
+extern "C" int sre_unwind(sre_ctx *ctx, uint8_t out_root[32])
+{
+    std::vector<sre_account_delta> acct;
+    std::vector<sre_storage_entry> st;
+    if (unwind_rows(ctx, "sre_unwind", acct, st))
+        return -1;
+    return sre_incremental_root(ctx, acct.data(), acct.size(), st.data(), st.size(),
+                                out_root);
+}
+
+extern "C" int sre_unwind_with_updates(sre_ctx *ctx, uint8_t out_root[32])
+{
+    std::vector<sre_account_delta> acct;
+    std::vector<sre_storage_entry> st;
+    if (unwind_rows(ctx, "sre_unwind_with_updates", acct, st))
+        return -1;
+    return sre_incremental_root_with_updates(ctx, acct.data(), acct.size(),
+                                             st.data(), st.size(), out_root);
+}
+
+extern "C" int sre_get_revert_counters(sre_ctx *ctx, uint64_t out[4])
+{
+    memcpy(out, ctx->rv_cnt, sizeof(ctx->rv_cnt));
     return 0;
 }

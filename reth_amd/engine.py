@@ -505,3 +505,61 @@ class StateRootEngine:
         return {"examined": out[0], "seeded": out[1], "rehashed": out[2],
                 "small_acct_merge": out[3], "small_st_merge": out[4],
                 "captured": out[5]}
+
+    # ---- revert capture and unwind ----
+    def capture_reverts(self, on: bool):
+        """Turn revert capture on or off (off by default). While on, every
+        successful apply_delta / incremental_root /
+        incremental_root_with_updates / root_from_nodes also stores the
+        delta that undoes it (include/sre.h sre_set_revert_capture); only
+        the last one is kept. Turning it off drops the stored revert."""
+        self._check(self._lib.sre_set_revert_capture(
+            ctypes.c_void_p(self._ctx), ctypes.c_int(1 if on else 0)))
+
+    def revert_counts(self):
+        """(account rows, storage rows) of the stored revert; (0, 0) when
+        none is stored."""
+        na, ns = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.sre_revert_counts(
+            ctypes.c_void_p(self._ctx), ctypes.byref(na), ctypes.byref(ns)))
+        return na.value, ns.value
+
+    def revert(self):
+        """The stored revert as (DELTA_DTYPE array, STORAGE_DTYPE array): a
+        valid delta over the current state that restores, row for row, the
+        state before the last captured delta. Keep it to unwind more than
+        one block: apply the fetched reverts newest first through
+        incremental_root."""
+        na, ns = self.revert_counts()
+        acct = np.zeros(na, dtype=DELTA_DTYPE)
+        st = np.zeros(ns, dtype=STORAGE_DTYPE)
+        self._check(self._lib.sre_revert_get(
+            ctypes.c_void_p(self._ctx), _np_ptr(acct), ctypes.c_uint64(na),
+            _np_ptr(st), ctypes.c_uint64(ns)))
+        return acct, st
+
+    def unwind(self) -> bytes:
+        """incremental_root over the stored revert: the resident state and
+        the root go back to before the last captured delta (the unwind of
+        MerkleStage). With capture on, the stored revert becomes the redo.
+        Raises with `no-revert-captured` when nothing is stored."""
+        out = (ctypes.c_uint8 * 32)()
+        self._check(self._lib.sre_unwind(ctypes.c_void_p(self._ctx), out))
+        return bytes(out)
+
+    def unwind_with_updates(self):
+        """incremental_root_with_updates over the stored revert: (root, net
+        row diff against the trie before the unwind)."""
+        out = (ctypes.c_uint8 * 32)()
+        self._check(self._lib.sre_unwind_with_updates(
+            ctypes.c_void_p(self._ctx), out))
+        return bytes(out), self._fetch_updates()
+
+    def revert_counters(self) -> dict:
+        """What the last revert capture did (include/sre.h
+        sre_get_revert_counters)."""
+        out = (ctypes.c_uint64 * 4)()
+        self._check(self._lib.sre_get_revert_counters(
+            ctypes.c_void_p(self._ctx), out))
+        return {"acct_rows": out[0], "st_rows": out[1], "wiped_rows": out[2],
+                "no_row": out[3]}
