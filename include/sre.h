@@ -182,6 +182,26 @@ void     sre_destroy(sre_ctx *ctx);
 int sre_upload_accounts(sre_ctx *ctx, const sre_account_entry *entries, uint64_t n);
 int sre_upload_storage(sre_ctx *ctx, const sre_storage_entry *entries, uint64_t n);
 
+/* Borrow sorted entries that already live in device memory (zero-copy):
+ * d_entries points at n sre_account_entry / sre_storage_entry rows under
+ * the input contract above. The caller keeps the memory alive, and does not
+ * write it, until the resident state is replaced (another upload or set
+ * call, or a delta merge, which adopts engine-owned copies). The same entry
+ * limit as at upload; replaces the state and disarms retention like one. */
+int sre_set_accounts_device(sre_ctx *ctx, const void *d_entries, uint64_t n);
+int sre_set_storage_device(sre_ctx *ctx, const void *d_entries, uint64_t n);
+
+/* keccak256 of n messages of `len` bytes in device memory, message i at
+ * d_in + i * stride; d_out receives n * 32 bytes. The kernel runs on the
+ * engine's own stream, which is drained before the call returns: writes to
+ * d_in queued on another stream must have completed before the call.
+ * sre_keccak_batch_device hashes one keccak block per message and rejects
+ * len > 135; sre_keccak_long_device takes any len up to stride. */
+int sre_keccak_batch_device(sre_ctx *ctx, const void *d_in, uint64_t stride,
+                            uint32_t len, uint64_t n, void *d_out);
+int sre_keccak_long_device(sre_ctx *ctx, const void *d_in, uint64_t stride,
+                           uint32_t len, uint64_t n, void *d_out);
+
 /* Compute the state root over the uploaded entries.
  * Equivalent surface: StateRoot::root() (crates/trie/trie/src/trie.rs:154). */
 int sre_root(sre_ctx *ctx, uint8_t out_root[32]);

@@ -46,6 +46,8 @@
 #include <map>
 #include <array>
 #include <memory>
+#include <numeric>
+#include <optional>
 
 #include "../../include/sre.h"
 #include "junction.h"
@@ -1140,14 +1142,10 @@ __global__ void __launch_bounds__(BLOCK) k_level_gather(
 // ---------------------------------------------------------------------------
 
 #define SLOT_BR 552 // >= 4*136 zero-padded branch RLP slot in global scratch
-// Branch scratch layout: 1 = row-major (each group's padded RLP in its own
-// 576-B row, 9 cache lines, per-lane dense stores/loads served by L2
-// locality), 0 = column-major words (per-instruction coalescing, but
-// divergent flush timing scatters it). Measured choice — see profiles/.
-#ifndef SRE_SCRATCH_ROWMAJOR
-#define SRE_SCRATCH_ROWMAJOR 0 // measured: col 444.7 ms vs row 456.6 ms @10Mx64
-#endif
-#define SLOT_BR_ROW 576 // row stride, 64-B aligned
+// Branch scratch layout: column-major u64 words (word w of group g at
+// w * stride + g: per-instruction coalescing). A row-major layout (576-B row
+// per group) was tried and measured slower: col 444.7 ms vs row 456.6 ms
+// @10Mx64.
 #ifndef SRE_BR_CHUNK_MB
 #define SRE_BR_CHUNK_MB 16 // branch-pipeline chunk, Mi-groups. Measured:
 // 16 beats 8 (382.5 vs 385.0 ms at 10Mx64); 32 OOMs the ping-pong scratch.
@@ -1196,11 +1194,7 @@ struct byte_appender {
     {
         if (stride == 0) // direct row (fused kernel's LDS slot)
             return base + w;
-#if SRE_SCRATCH_ROWMAJOR
-        return base + (uint64_t)g * (SLOT_BR_ROW / 8) + w;
-#else
         return base + (uint64_t)w * stride + g;
-#endif
     }
     __device__ __forceinline__ void put(uint8_t v)
     {
@@ -1692,30 +1686,18 @@ __global__ void __launch_bounds__(BLOCK) k_branch_hash(
 #pragma unroll
         for (int i = 0; i < 25; ++i)
             s[i] = 0;
-#if SRE_SCRATCH_ROWMAJOR
-        const uint64_t *row = scr64 + (uint64_t)g * (SLOT_BR_ROW / 8);
-#endif
         for (int blk = 0; blk < nblocks; ++blk) {
 #pragma unroll
             for (int i = 0; i < 17; ++i)
-#if SRE_SCRATCH_ROWMAJOR
-                s[i] ^= row[blk * 17 + i];
-#else
                 s[i] ^= scr64[(uint64_t)(blk * 17 + i) * scratch_stride + g];
-#endif
             keccak_f(s);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             br_hash[i] = s[i];
     }
-#if SRE_SCRATCH_ROWMAJOR
-    const uint64_t *inl = scr64 + (uint64_t)g * (SLOT_BR_ROW / 8);
-    const uint64_t inl_stride = 1;
-#else
     const uint64_t *inl = scr64 + g;
     const uint64_t inl_stride = scratch_stride;
-#endif
     branch_tail(mt, subtree, keys, key_stride, br_hash, inl, inl_stride,
                 lds + (uint64_t)threadIdx.x * SLOT_EXT, recs, depths, n,
                 seg_roots, child_refs, child_lens, hist_l, bhash_by_s, urows,
@@ -2084,11 +2066,7 @@ __device__ __forceinline__ void proof_grab_one(
     uint64_t *dst = (uint64_t *)rows[r].rlp;
     int nw = (mt.br_len + 7) / 8;
     for (int w = 0; w < nw; ++w)
-#if SRE_SCRATCH_ROWMAJOR
-        dst[w] = scr64[(uint64_t)slot * (SLOT_BR_ROW / 8) + w];
-#else
         dst[w] = scr64[(uint64_t)w * scratch_stride + slot];
-#endif
 }
 
 // find the chunk-local group covering leaf index pos, or ~0u
@@ -4017,8 +3995,7 @@ static int select_level(sre_ctx *ctx, const level_in &in, level_bufs &bufs,
     const uint64_t BR_CHUNK = br_chunk_groups();
     HIP_CHECK(ctx, bufs.gs.alloc(((uint64_t)w.n_groups + 1) * 4));
     w.chunk = w.n_groups < BR_CHUNK ? w.n_groups : BR_CHUNK;
-    HIP_CHECK(ctx, bufs.scratch.alloc(w.chunk * (SRE_SCRATCH_ROWMAJOR
-                                                     ? SLOT_BR_ROW : SLOT_BR)));
+    HIP_CHECK(ctx, bufs.scratch.alloc(w.chunk * SLOT_BR));
     HIP_CHECK(ctx, bufs.meta.alloc(w.chunk * sizeof(br_meta)));
     if (in.updates_kind >= 0) {
         // per-level: capacity must cover THIS level's chunk
@@ -4082,8 +4059,7 @@ static int partition_classes(sre_ctx *ctx, const level_in &in, uint32_t n_pt,
     }
     w.pipe2 = w.n_groups > w.chunk; // >1 chunk: overlap pays for 2nd buf
     if (w.pipe2) {
-        HIP_CHECK(ctx, w.scratch2.alloc(w.chunk * (SRE_SCRATCH_ROWMAJOR
-                                                       ? SLOT_BR_ROW : SLOT_BR)));
+        HIP_CHECK(ctx, w.scratch2.alloc(w.chunk * SLOT_BR));
         HIP_CHECK(ctx, w.meta2.alloc(w.chunk * sizeof(br_meta)));
     }
     ctx->path_cnt[0] += w.use_cls;
@@ -4270,18 +4246,6 @@ static int run_levels(sre_ctx *ctx, const level_in &in, pass_out *po,
 // ---------------------------------------------------------------------------
 // passes
 // ---------------------------------------------------------------------------
-
-static void publish_stats(sre_ctx *ctx, const pass_out &po, double total_ms)
-{
-    ctx->stats.total_ms = total_ms;
-    ctx->stats.leaf_hash_ms = po.leaf_ms;
-    ctx->stats.leaf_count = po.leaf_count;
-    ctx->stats.leaf_blocks = po.leaf_blocks;
-    ctx->stats.branch_hash_ms = po.branch_ms;
-    ctx->stats.branch_count = po.branch_count;
-    ctx->stats.branch_blocks = po.branch_blocks;
-    ctx->stats.levels = po.levels;
-}
 
 // A sorted storage array cut into per-account segments (one storage trie
 // each): seg_id[i] = segment of entry i, lcp = neighbour common prefixes
@@ -4487,6 +4451,50 @@ static int run_storage_intervals(sre_ctx *ctx, const uint32_t *d_lo,
                             {compact.as<sre_storage_entry>(), total});
 }
 
+// Everything after the account leaf kernel: read the device histogram back,
+// run the account trie's levels and clear the segment stash of the rows they
+// emit (account rows carry no acct_key). bhash is allocated here when updates
+// are retained, unless the caller seeded it. n_inputs: the histogram's total.
+static int run_account_levels(sre_ctx *ctx, DBuf &recs, DBuf &depths,
+                              const int8_t *lcp, DBuf &hist, DBuf &bhash,
+                              int subtree, uint8_t *d_roots, uint8_t *d_child_refs,
+                              uint8_t *d_child_lens, pass_out *po, uint32_t *d_err,
+                              const cell_capture &cap = {},
+                              const proof_capture &proof = {},
+                              uint64_t *n_inputs = nullptr)
+{
+    uint64_t na = ctx->acct.n;
+    uint32_t hist_host[66];
+    HIP_CHECK(ctx, hipMemcpy(hist_host, hist.p, 66 * 4, hipMemcpyDeviceToHost));
+    if (n_inputs)
+        *n_inputs = std::accumulate(hist_host, hist_host + 66, (uint64_t)0);
+    if (ctx->retain_updates && !bhash.p)
+        HIP_CHECK(ctx, bhash.alloc(na * 32));
+    size_t upd_start = ctx->updates.size();
+    level_in in;
+    in.n = na;
+    in.recs = recs.as<node_rec>();
+    in.depths = depths.as<uint8_t>();
+    in.lcp = lcp;
+    in.keys = (const uint8_t *)ctx->acct.d + offsetof(sre_account_entry, key);
+    in.key_stride = sizeof(sre_account_entry);
+    in.hist_host = hist_host;
+    in.subtree = subtree;
+    in.seg_roots = d_roots;
+    in.child_refs = d_child_refs;
+    in.child_lens = d_child_lens;
+    in.err = d_err;
+    in.updates_kind = ctx->retain_updates ? 0 : -1;
+    in.bhash = bhash.as<uint8_t>();
+    if (run_levels(ctx, in, po, cap, proof))
+        return -1;
+    if (ctx->retain_updates) {
+        for (size_t r = upd_start; r < ctx->updates.size(); ++r)
+            memset(ctx->updates[r].pad_, 0, sizeof(ctx->updates[r].pad_));
+    }
+    return 0;
+}
+
 static int run_account_pass(sre_ctx *ctx, const uint8_t *d_storage_roots, int subtree,
                             uint8_t *d_roots, uint8_t *d_child_refs,
                             uint8_t *d_child_lens, pass_out *po, uint32_t *d_err,
@@ -4524,36 +4532,82 @@ static int run_account_pass(sre_ctx *ctx, const uint8_t *d_storage_roots, int su
     if (check_err(ctx, d_err))
         return -1;
 
-    uint32_t hist_host[66];
-    HIP_CHECK(ctx, hipMemcpy(hist_host, hist.p, 66 * 4, hipMemcpyDeviceToHost));
-
     DBuf bhash(ctx);
-    if (ctx->retain_updates)
-        HIP_CHECK(ctx, bhash.alloc(na * 32));
-    size_t upd_start = ctx->updates.size();
-    level_in in;
-    in.n = na;
-    in.recs = recs.as<node_rec>();
-    in.depths = depths.as<uint8_t>();
-    in.lcp = lcp.as<int8_t>();
-    in.keys = (const uint8_t *)ctx->acct.d + offsetof(sre_account_entry, key);
-    in.key_stride = sizeof(sre_account_entry);
-    in.hist_host = hist_host;
-    in.subtree = subtree;
-    in.seg_roots = d_roots;
-    in.child_refs = d_child_refs;
-    in.child_lens = d_child_lens;
-    in.err = d_err;
-    in.updates_kind = ctx->retain_updates ? 0 : -1;
-    in.bhash = bhash.as<uint8_t>();
-    if (run_levels(ctx, in, po, cap, proof))
+    return run_account_levels(ctx, recs, depths, lcp.as<int8_t>(), hist, bhash,
+                              subtree, d_roots, d_child_refs, d_child_lens, po,
+                              d_err, cap, proof);
+}
+
+// A cell-top capture armed for one account pass (dirty-path retention):
+// rows go to ctx->cap_rows, grown to fit na accounts, their count to cnt.
+struct armed_capture {
+    sre_ctx *ctx;
+    DBuf cnt{ctx};
+    cell_capture cap;
+    int arm(uint64_t na);
+    int read(); // after the pass: the captured row count, into ctx->cap_count
+};
+
+// capture-row capacity for a state of na accounts
+static uint64_t cap_rows_for(uint64_t na)
+{
+    return 2 * (na < (uint64_t)N_CELLS ? na : (uint64_t)N_CELLS) + 8192;
+}
+
+int armed_capture::arm(uint64_t na)
+{
+    if (ctx->cap_rows.grow(ctx, cap_rows_for(na), sizeof(cap_row)))
         return -1;
-    if (ctx->retain_updates) {
-        for (size_t r = upd_start; r < ctx->updates.size(); ++r)
-            memset(ctx->updates[r].pad_, 0, sizeof(ctx->updates[r].pad_));
-    }
+    HIP_CHECK(ctx, cnt.alloc(4));
+    HIP_CHECK(ctx, hipMemsetAsync(cnt.p, 0, 4, ctx->stream));
+    cap = {CELL_NIBBLES, (cap_row *)ctx->cap_rows.p, cnt.as<uint32_t>(),
+           ctx->cap_rows.cap};
     return 0;
 }
+
+int armed_capture::read()
+{
+    uint32_t n = 0;
+    HIP_CHECK(ctx, hipMemcpy(&n, cnt.p, 4, hipMemcpyDeviceToHost));
+    ctx->cap_count = n;
+    return 0;
+}
+
+// What a root-type entry point carries through its passes: the device error
+// flag, the pass totals and the whole-call timer. start_timer() and arm_err()
+// stand where each entry point starts its clock and first needs its flag.
+struct root_call {
+    sre_ctx *ctx;
+    DBuf err{ctx};
+    pass_out po;
+    std::optional<EvTimer> whole; // created by start_timer(), on ctx->device
+    uint32_t *flag() { return err.as<uint32_t>(); }
+    int begin(bool zero_stats) { return begin_call(ctx, zero_stats); }
+    int start_timer()
+    {
+        HIP_CHECK(ctx, whole.emplace().start(ctx->stream));
+        return 0;
+    }
+    int arm_err() { return alloc_err_flag(ctx, err); }
+    int publish() // stop the clock, drain the stream, publish the stats
+    {
+        HIP_CHECK(ctx, whole->stop(ctx->stream));
+        HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        float total = 0;
+        HIP_CHECK(ctx, whole->ms(&total));
+        ctx->stats.total_ms = total;
+        ctx->stats.leaf_hash_ms = po.leaf_ms;
+        ctx->stats.leaf_count = po.leaf_count;
+        ctx->stats.leaf_blocks = po.leaf_blocks;
+        ctx->stats.branch_hash_ms = po.branch_ms;
+        ctx->stats.branch_count = po.branch_count;
+        ctx->stats.branch_blocks = po.branch_blocks;
+        ctx->stats.levels = po.levels;
+        return 0;
+    }
+    // the flag must be clean
+    int finish() { return check_err(ctx, flag()) ? -1 : publish(); }
+};
 
 // The one vocabulary of validation failures (sre.h "Failed calls"): device
 // flags and host-side checks both report through here, so one kind of bad
@@ -4591,6 +4645,17 @@ static const uint8_t EMPTY_ROOT_H[32] = {
     0x92, 0xc0, 0xf8, 0x6e, 0x5b, 0x48, 0xe0, 0x1b, 0x99, 0x6c, 0xad, 0xc0,
     0x01, 0x62, 0x2f, 0xb5, 0xe3, 0x63, 0xb4, 0x21,
 };
+
+// No accounts: the empty root, or an error when storage rows are resident.
+static int empty_state_root(sre_ctx *ctx, uint8_t out_root[32])
+{
+    if (ctx->st.n != 0) {
+        set_err(ctx, "storage entries without accounts");
+        return -1;
+    }
+    memcpy(out_root, EMPTY_ROOT_H, 32);
+    return 0;
+}
 
 // ---------------------------------------------------------------------------
 // multiproofs (sre_account_proof / sre_storage_proof). The device side
@@ -4914,47 +4979,30 @@ extern "C" int sre_storage_proof(sre_ctx *ctx, const uint8_t *acct_keys,
 
 extern "C" int sre_root(sre_ctx *ctx, uint8_t out_root[32])
 {
-    if (begin_call(ctx, true))
+    root_call f{ctx};
+    if (f.begin(true))
         return -1;
-    if (ctx->acct.n == 0) {
-        if (ctx->st.n != 0) {
-            set_err(ctx, "storage entries without accounts");
-            return -1;
-        }
-        memcpy(out_root, EMPTY_ROOT_H, 32);
-        return 0;
-    }
-    EvTimer whole;
-    HIP_CHECK(ctx, whole.start(ctx->stream));
-
-    DBuf err(ctx), acct_roots(ctx), root(ctx);
-    if (alloc_err_flag(ctx, err))
+    if (ctx->acct.n == 0)
+        return empty_state_root(ctx, out_root);
+    DBuf acct_roots(ctx), root(ctx);
+    if (f.start_timer() || f.arm_err())
         return -1;
     HIP_CHECK(ctx, acct_roots.alloc(ctx->acct.n * 32));
     HIP_CHECK(ctx, root.alloc(32));
 
-    pass_out po;
-    if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &po, err.as<uint32_t>()))
+    if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &f.po, f.flag()) ||
+        run_account_pass(ctx, acct_roots.as<uint8_t>(), 0, root.as<uint8_t>(),
+                         nullptr, nullptr, &f.po, f.flag()) ||
+        f.finish())
         return -1;
-    if (run_account_pass(ctx, acct_roots.as<uint8_t>(), 0, root.as<uint8_t>(),
-                         nullptr, nullptr, &po, err.as<uint32_t>()))
-        return -1;
-    if (check_err(ctx, err.as<uint32_t>()))
-        return -1;
-
-    HIP_CHECK(ctx, whole.stop(ctx->stream));
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    float total = 0;
-    HIP_CHECK(ctx, whole.ms(&total));
-    publish_stats(ctx, po, total);
-
     HIP_CHECK(ctx, hipMemcpy(out_root, root.p, 32, hipMemcpyDeviceToHost));
     return 0;
 }
 
 extern "C" int sre_storage_roots(sre_ctx *ctx, uint8_t *out, uint64_t n)
 {
-    if (begin_call(ctx, false))
+    root_call f{ctx}; // untimed, and the previous call's stats stay
+    if (f.begin(false))
         return -1;
     if (n != ctx->acct.n) {
         set_err(ctx, "sre_storage_roots: n != uploaded account count");
@@ -4962,14 +5010,12 @@ extern "C" int sre_storage_roots(sre_ctx *ctx, uint8_t *out, uint64_t n)
     }
     if (n == 0)
         return 0;
-    DBuf err(ctx), acct_roots(ctx);
-    if (alloc_err_flag(ctx, err))
+    DBuf acct_roots(ctx);
+    if (f.arm_err())
         return -1;
     HIP_CHECK(ctx, acct_roots.alloc(ctx->acct.n * 32));
-    pass_out po;
-    if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &po, err.as<uint32_t>()))
-        return -1;
-    if (check_err(ctx, err.as<uint32_t>()))
+    if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &f.po, f.flag()) ||
+        check_err(ctx, f.flag()))
         return -1;
     HIP_CHECK(ctx, hipMemcpy(out, acct_roots.p, ctx->acct.n * 32, hipMemcpyDeviceToHost));
     return 0;
@@ -4979,17 +5025,15 @@ extern "C" int sre_subtree_roots(sre_ctx *ctx, uint8_t out_child_refs[16][33],
                                  uint8_t out_child_lens[16],
                                  uint8_t out_root_hash[16][32], uint64_t out_counts[16])
 {
-    if (begin_call(ctx, true))
+    root_call f{ctx};
+    if (f.begin(true))
         return -1;
     memset(out_child_lens, 0, 16);
     memset(out_counts, 0, 16 * 8);
     if (ctx->acct.n == 0)
         return 0;
-    EvTimer whole;
-    HIP_CHECK(ctx, whole.start(ctx->stream));
-
-    DBuf err(ctx), acct_roots(ctx), roots(ctx), crefs(ctx), clens(ctx), counts(ctx);
-    if (alloc_err_flag(ctx, err))
+    DBuf acct_roots(ctx), roots(ctx), crefs(ctx), clens(ctx), counts(ctx);
+    if (f.start_timer() || f.arm_err())
         return -1;
     HIP_CHECK(ctx, acct_roots.alloc(ctx->acct.n * 32));
     HIP_CHECK(ctx, roots.alloc(16 * 32));
@@ -5003,23 +5047,15 @@ extern "C" int sre_subtree_roots(sre_ctx *ctx, uint8_t out_child_refs[16][33],
     HIP_CHECK(ctx, hipMemsetAsync(crefs.p, 0, 16 * 33, ctx->stream));
     HIP_CHECK(ctx, hipMemsetAsync(roots.p, 0, 16 * 32, ctx->stream));
 
-    pass_out po;
-    if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &po, err.as<uint32_t>()))
-        return -1;
-    if (run_account_pass(ctx, acct_roots.as<uint8_t>(), 1, roots.as<uint8_t>(),
-                         crefs.as<uint8_t>(), clens.as<uint8_t>(), &po,
-                         err.as<uint32_t>()))
+    if (run_storage_pass(ctx, acct_roots.as<uint8_t>(), &f.po, f.flag()) ||
+        run_account_pass(ctx, acct_roots.as<uint8_t>(), 1, roots.as<uint8_t>(),
+                         crefs.as<uint8_t>(), clens.as<uint8_t>(), &f.po,
+                         f.flag()))
         return -1;
     LAUNCH(ctx, k_nibble_counts, grid_for(ctx->acct.n), BLOCK, ctx->stream,
            ctx->acct.d, ctx->acct.n, counts.as<uint64_t>());
-    if (check_err(ctx, err.as<uint32_t>()))
+    if (f.finish())
         return -1;
-    HIP_CHECK(ctx, whole.stop(ctx->stream));
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    float total = 0;
-    HIP_CHECK(ctx, whole.ms(&total));
-    publish_stats(ctx, po, total);
-
     HIP_CHECK(ctx, hipMemcpy(out_child_refs, crefs.p, 16 * 33, hipMemcpyDeviceToHost));
     HIP_CHECK(ctx, hipMemcpy(out_child_lens, clens.p, 16, hipMemcpyDeviceToHost));
     HIP_CHECK(ctx, hipMemcpy(out_root_hash, roots.p, 16 * 32, hipMemcpyDeviceToHost));
@@ -5487,61 +5523,247 @@ static int apply_delta_small(sre_ctx *ctx, const sre_account_delta *acct_delta,
     return 0;
 }
 
-// capture-row capacity for a state of na accounts
-static uint64_t cap_rows_for(uint64_t na)
-{
-    return 2 * (na < (uint64_t)N_CELLS ? na : (uint64_t)N_CELLS) + 8192;
-}
-
 // Full root, retaining the cell-top records and per-account storage roots
-// for subsequent sre_incremental_root calls (dirty-path incremental).
+// for subsequent sre_incremental_root calls (dirty-path incremental). It
+// times nothing and publishes no stats (they stay zeroed): no finish().
 extern "C" int sre_root_retaining(sre_ctx *ctx, uint8_t out_root[32])
 {
-    if (begin_call(ctx, true))
+    root_call f{ctx};
+    if (f.begin(true))
         return -1;
     invalidate_retention(ctx);
-    if (ctx->cap_rows.grow(ctx, cap_rows_for(ctx->acct.n), sizeof(cap_row)))
-        return -1;
     if (ctx->acct.n == 0) {
-        if (ctx->st.n != 0) {
-            set_err(ctx, "storage entries without accounts");
+        if (empty_state_root(ctx, out_root))
             return -1;
-        }
         ctx->cap_count = 0;
         ctx->cells_valid = true;
-        memcpy(out_root, EMPTY_ROOT_H, 32);
         return 0;
     }
-    if (ctx->roots_ret.grow(ctx, ctx->acct.n, 32))
-        return -1;
-    DBuf err(ctx), roots(ctx), capcnt(ctx);
-    if (alloc_err_flag(ctx, err))
+    DBuf roots(ctx);
+    armed_capture cap{ctx};
+    if (ctx->roots_ret.grow(ctx, ctx->acct.n, 32) || f.arm_err())
         return -1;
     HIP_CHECK(ctx, roots.alloc(32));
-    HIP_CHECK(ctx, capcnt.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(capcnt.p, 0, 4, ctx->stream));
-    pass_out po;
+    if (cap.arm(ctx->acct.n))
+        return -1;
     // full storage pass into the RETAINED roots buffer (chained deltas
     // carry and patch it instead of recomputing every segment)
-    if (run_storage_pass(ctx, (uint8_t *)ctx->roots_ret.p, &po,
-                         err.as<uint32_t>()))
+    if (run_storage_pass(ctx, (uint8_t *)ctx->roots_ret.p, &f.po, f.flag()) ||
+        run_account_pass(ctx, (const uint8_t *)ctx->roots_ret.p, 0,
+                         roots.as<uint8_t>(), nullptr, nullptr, &f.po, f.flag(),
+                         cap.cap) ||
+        check_err(ctx, f.flag()) || cap.read())
         return -1;
-    cell_capture cap;
-    cap.depth = CELL_NIBBLES;
-    cap.rows = (cap_row *)ctx->cap_rows.p;
-    cap.count = capcnt.as<uint32_t>();
-    cap.capacity = ctx->cap_rows.cap;
-    if (run_account_pass(ctx, (const uint8_t *)ctx->roots_ret.p, 0,
-                         roots.as<uint8_t>(), nullptr, nullptr,
-                         &po, err.as<uint32_t>(), cap))
-        return -1;
-    if (check_err(ctx, err.as<uint32_t>()))
-        return -1;
-    uint32_t cnt = 0;
-    HIP_CHECK(ctx, hipMemcpy(&cnt, capcnt.p, 4, hipMemcpyDeviceToHost));
-    ctx->cap_count = cnt;
     ctx->cells_valid = true;
     HIP_CHECK(ctx, hipMemcpy(out_root, roots.p, 32, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// What the steps of the dirty-path incremental root share (the shape of
+// delta_merge): the delta, the call frame, which merge ran, and the buffers
+// that live from the step that fills them to the end of the call.
+struct inc_root {
+    sre_ctx *ctx;
+    const sre_account_delta *acct_delta;
+    uint64_t n_acct;
+    const sre_storage_entry *st_delta;
+    uint64_t n_st;
+    std::vector<uint8_t> *bitmap_out; // with updates: the final dirty cells
+    root_call f{ctx};
+    // no_storage: accounts-only state and delta, new_roots is null (the leaf
+    // kernel substitutes EMPTY_ROOT). small / st_closed_form: the merges run.
+    bool no_storage = false, small = false, st_closed_form = false;
+    uint8_t *new_roots = nullptr;
+    uint32_t n_active = 0;
+    // map: old -> new positions; bitmap: dirty cells; dl / dls: the delta
+    DBuf map{ctx}, bitmap{ctx}, dl{ctx}, dls{ctx}, recs{ctx}, depths{ctx},
+        covered{ctx}, hist{ctx}, abhash{ctx}, alist{ctx}, roots{ctx};
+};
+
+// Step 1: merge the delta into the resident state (small or general merge),
+// carrying the retained storage roots into the ping-pong partner buffer.
+static int inc_merge(inc_root &r)
+{
+    sre_ctx *ctx = r.ctx;
+    r.no_storage = (ctx->st.n == 0 && r.n_st == 0);
+    // new roots buffer: the ping-pong partner of the retained one (no
+    // per-step hipMalloc at steady state), EMPTY-filled upper bound,
+    // carried across the merge
+    uint64_t max_na = ctx->acct.n + r.n_acct;
+    if (!r.no_storage && ctx->roots_ret2.grow(ctx, max_na, 32))
+        return -1;
+    r.new_roots = r.no_storage ? nullptr : (uint8_t *)ctx->roots_ret2.p;
+    if (r.new_roots)
+        LAUNCH(ctx, k_fill_empty_roots, grid_for(max_na ? max_na : 1), BLOCK,
+               ctx->stream, r.new_roots, max_na ? max_na : 1);
+
+    // small accounts-only deltas take the one-pass merge with lcp repair
+    // (closed-form ranks; O(delta) boundary lcps patched) — the scan-floor
+    // fix for the configs[4] shape. Everything else keeps the general
+    // overlay merge.
+    r.small = r.no_storage && r.n_acct > 0 && ctx->lcp_valid &&
+              (r.n_acct <= (ctx->acct.n >> 6) ||
+               (getenv("SRE_SD_FORCE") && r.n_acct <= ctx->acct.n));
+    if (r.small)
+        return apply_delta_small(ctx, r.acct_delta, r.n_acct, &r.map);
+    // carry only when the pre-delta state HAS storage: while ns stays 0
+    // every retained root is EMPTY_ROOT (and accounts-only fast-path
+    // deltas may have drifted roots_ret's indexing — harmless, since
+    // it is then never read)
+    merge_io io;
+    io.map_out = &r.map;
+    if (r.new_roots && ctx->st.n > 0)
+        io.d_old_roots = (const uint8_t *)ctx->roots_ret.p;
+    io.d_new_roots = r.new_roots;
+    if (merge_delta(ctx, r.acct_delta, r.n_acct, r.st_delta, r.n_st, io))
+        return -1;
+    r.st_closed_form = io.st_closed_form;
+    ctx->lcp_valid = false; // recomputed by inc_seed_and_rehash
+    return 0;
+}
+
+// Step 2: mark the 5-nibble cells the delta's rows fall into.
+static int inc_mark_cells(inc_root &r)
+{
+    sre_ctx *ctx = r.ctx;
+    HIP_CHECK(ctx, r.bitmap.alloc(N_CELLS));
+    HIP_CHECK(ctx, hipMemsetAsync(r.bitmap.p, 0, N_CELLS, ctx->stream));
+    if (to_device(ctx, r.dl, r.acct_delta, r.n_acct))
+        return -1;
+    if (r.n_acct)
+        LAUNCH(ctx, k_mark_delta_cells, grid_for(r.n_acct), BLOCK, ctx->stream,
+               r.dl.as<sre_account_delta>(), r.n_acct, r.bitmap.as<uint8_t>());
+    if (r.n_st) {
+        if (to_device(ctx, r.dls, r.st_delta, r.n_st))
+            return -1;
+        LAUNCH(ctx, k_mark_delta_cells_st, grid_for(r.n_st), BLOCK, ctx->stream,
+               r.dls.as<sre_storage_entry>(), r.n_st, r.bitmap.as<uint8_t>());
+    }
+    return 0;
+}
+
+// Step 3: recompute ONLY the touched accounts' storage tries: gather their
+// merged segments and scatter their fresh roots over the carried ones.
+static int inc_touched_storage(inc_root &r)
+{
+    sre_ctx *ctx = r.ctx;
+    if (!r.n_st)
+        return 0;
+    std::vector<key32> tkeys = storage_delta_accounts(r.st_delta, r.n_st);
+    uint32_t nt = (uint32_t)tkeys.size();
+    DBuf dtk(ctx), tlo(ctx), thi(ctx), taidx(ctx);
+    if (to_device(ctx, dtk, tkeys.data(), nt))
+        return -1;
+    HIP_CHECK(ctx, tlo.alloc((uint64_t)nt * 4));
+    HIP_CHECK(ctx, thi.alloc((uint64_t)nt * 4));
+    HIP_CHECK(ctx, taidx.alloc((uint64_t)nt * 4));
+    LAUNCH(ctx, k_touched_bounds, grid_for(nt), BLOCK, ctx->stream, ctx->st.d,
+           ctx->st.n, ctx->acct.d, ctx->acct.n, dtk.as<uint8_t>(), nt,
+           tlo.as<uint32_t>(), thi.as<uint32_t>(), taidx.as<uint32_t>(),
+           r.new_roots, r.f.flag());
+    std::vector<uint32_t> lo, hi;
+    if (to_host(ctx, lo, tlo, nt) || to_host(ctx, hi, thi, nt))
+        return -1;
+    std::vector<uint32_t> offs = interval_offsets(lo, hi);
+    if (offs[nt] &&
+        run_storage_intervals(ctx, tlo.as<uint32_t>(), thi.as<uint32_t>(), offs,
+                              r.new_roots, &r.f.po, r.f.flag()))
+        return -1;
+    return check_err(ctx, r.f.flag());
+}
+
+// Step 4: the account lcp (in the retained ping-pong buffer: repaired by the
+// small merge, recomputed here after the general one, arming repair for the
+// next delta). Then seed the clean cell tops from the retained rows and
+// rehash the leaves of dirty cells and of positions no seed covers.
+static int inc_seed_and_rehash(inc_root &r)
+{
+    sre_ctx *ctx = r.ctx;
+    uint64_t na = ctx->acct.n;
+    if (!r.small) {
+        if (ctx->lcp_ret.grow(ctx, na + 1))
+            return -1;
+        LAUNCH(ctx, k_lcp_account, grid_for(na + 1), BLOCK, ctx->stream,
+               ctx->acct.d, na, 0, (int8_t *)ctx->lcp_ret.p, r.f.flag());
+        ctx->lcp_valid = true;
+    }
+    int8_t *lcp_p = (int8_t *)ctx->lcp_ret.p;
+    HIP_CHECK(ctx, r.recs.alloc(na * sizeof(node_rec)));
+    HIP_CHECK(ctx, r.depths.alloc(na));
+    HIP_CHECK(ctx, r.covered.alloc(na));
+    HIP_CHECK(ctx, r.hist.alloc(66 * 4));
+    HIP_CHECK(ctx, r.roots.alloc(32));
+    HIP_CHECK(ctx, hipMemsetAsync(r.depths.p, 0xFF, na, ctx->stream));
+    HIP_CHECK(ctx, hipMemsetAsync(r.covered.p, 0, na, ctx->stream));
+    HIP_CHECK(ctx, hipMemsetAsync(r.hist.p, 0, 66 * 4, ctx->stream));
+    // with updates the seeded rows bring their branch hashes along
+    if (ctx->retain_updates)
+        HIP_CHECK(ctx, r.abhash.alloc(na * 32));
+    // seed clean cell-tops; anything invalid dirties its cell
+    if (ctx->cap_count)
+        LAUNCH(ctx, k_revalidate_rows, grid_for(ctx->cap_count), BLOCK,
+               ctx->stream, (const cap_row *)ctx->cap_rows.p, ctx->cap_count,
+               r.map.as<uint32_t>(), lcp_p, r.bitmap.as<uint8_t>(),
+               r.recs.as<node_rec>(), r.depths.as<uint8_t>(),
+               r.covered.as<uint8_t>(), r.hist.as<uint32_t>(),
+               r.abhash.as<uint8_t>());
+    EvTimer leaf;
+    HIP_CHECK(ctx, leaf.start(ctx->stream));
+    // compact the recompute set (covered == 0: dirty cells leave their
+    // positions uncovered, so this is exactly dirty ∪ uncovered) and
+    // launch the leaf kernel over it instead of sweeping all na lanes
+    {
+        uint32_t nblk = grid_for(na);
+        DBuf ac(ctx), ao(ctx);
+        HIP_CHECK(ctx, ac.alloc((uint64_t)nblk * 4));
+        HIP_CHECK(ctx, ao.alloc((uint64_t)nblk * 4));
+        LAUNCH(ctx, k_active_hist, nblk, BLOCK, ctx->stream,
+               r.covered.as<uint8_t>(), na, ac.as<uint32_t>());
+        if (scan_u32(ctx, ac.as<uint32_t>(), ao.as<uint32_t>(), nblk,
+                     &r.n_active))
+            return -1;
+        HIP_CHECK(ctx, r.alist.alloc(((uint64_t)r.n_active ? r.n_active : 1) * 4));
+        LAUNCH(ctx, k_active_scatter, nblk, BLOCK, ctx->stream,
+               r.covered.as<uint8_t>(), na, ao.as<uint32_t>(),
+               r.alist.as<uint32_t>());
+    }
+    if (r.n_active)
+        LAUNCH(ctx, k_leaf_account, grid_for(r.n_active), BLOCK, ctx->stream,
+               ctx->acct.d, na, (const uint8_t *)r.new_roots, lcp_p, 0,
+               r.recs.as<node_rec>(), r.depths.as<uint8_t>(),
+               r.hist.as<uint32_t>(), r.roots.as<uint8_t>(), nullptr, nullptr,
+               nullptr, nullptr, r.alist.as<uint32_t>(), r.n_active);
+    HIP_CHECK(ctx, leaf.stop(ctx->stream));
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    HIP_CHECK(ctx, leaf.ms(&ms));
+    r.f.po.leaf_ms += ms;
+    if (check_err(ctx, r.f.flag()))
+        return -1;
+    // final dirty-cell set (incl. revalidation misses)
+    return r.bitmap_out ? to_host(ctx, *r.bitmap_out, r.bitmap, N_CELLS) : 0;
+}
+
+// Step 5: the account trie's levels, with a fresh capture for the next
+// delta. k_revalidate_rows has consumed the retained rows, so capturing over
+// the same buffer is safe (arm() swaps in a bigger one when na outgrew it).
+static int inc_account_levels(inc_root &r)
+{
+    sre_ctx *ctx = r.ctx;
+    armed_capture cap{ctx};
+    // every rehashed leaf (k_leaf_account) and every seeded row
+    // (k_revalidate_rows) adds exactly one to hist
+    uint64_t level_inputs = 0;
+    if (cap.arm(ctx->acct.n) ||
+        run_account_levels(ctx, r.recs, r.depths, (const int8_t *)ctx->lcp_ret.p,
+                           r.hist, r.abhash, 0, r.roots.as<uint8_t>(), nullptr,
+                           nullptr, &r.f.po, r.f.flag(), cap.cap, {},
+                           &level_inputs) ||
+        check_err(ctx, r.f.flag()) || cap.read())
+        return -1;
+    ctx->inc_cnt[1] = level_inputs - r.n_active;
+    ctx->inc_cnt[2] = r.n_active;
+    ctx->inc_cnt[5] = ctx->cap_count;
     return 0;
 }
 
@@ -5549,262 +5771,51 @@ extern "C" int sre_root_retaining(sre_ctx *ctx, uint8_t out_root[32])
 // (accounts + storage) and recompute only the 5-nibble cells it touches —
 // reusing every clean cell-top record and every untouched account's
 // retained storage root (the §3b walker-skip semantics expressed in this
-// engine's level machinery). Requires a prior sre_root_retaining.
-// with_updates: ctx->retain_updates is armed by the caller; additionally
-// seeds bhash from the captured rows and copies the final dirty-cell
-// bitmap out for the host-side net diff.
-static int incremental_root_impl(sre_ctx *ctx,
-                                 const sre_account_delta *acct_delta,
-                                 uint64_t n_acct,
-                                 const sre_storage_entry *st_delta,
+// engine's level machinery). Requires a prior sre_root_retaining. With
+// ctx->retain_updates armed by the caller, the seeded rows also seed bhash
+// and the final dirty-cell bitmap goes to bitmap_out for the net diff.
+// Retention is valid on entry, disarmed the moment the merge has adopted the
+// new state and armed again only by the commit at the end: a step that fails
+// in between returns with it disarmed; a rejected delta adopted nothing.
+static int incremental_root_impl(sre_ctx *ctx, const sre_account_delta *acct_delta,
+                                 uint64_t n_acct, const sre_storage_entry *st_delta,
                                  uint64_t n_st, uint8_t out_root[32],
-                                 bool with_updates,
                                  std::vector<uint8_t> *bitmap_out)
 {
-    if (begin_call(ctx, true))
+    inc_root r{ctx, acct_delta, n_acct, st_delta, n_st, bitmap_out};
+    if (r.f.begin(true))
         return -1;
     if (!ctx->cells_valid) {
         set_err(ctx, "sre_incremental_root: needs sre_root_retaining first");
         return -1;
     }
-    EvTimer whole;
-    HIP_CHECK(ctx, whole.start(ctx->stream));
-    ctx->inc_cnt[0] = ctx->cap_count;
-
-    // accounts-only states with accounts-only deltas skip the roots
-    // machinery entirely (every storage root is EMPTY_ROOT; the leaf
-    // kernel's null-roots path substitutes it) — the configs[4] shape
-    bool no_storage = (ctx->st.n == 0 && n_st == 0);
-    // new roots buffer: the ping-pong partner of the retained one (no
-    // per-step hipMalloc at steady state), EMPTY-filled upper bound,
-    // carried across the merge
-    uint64_t max_na = ctx->acct.n + n_acct;
-    if (!no_storage && ctx->roots_ret2.grow(ctx, max_na, 32))
+    if (r.f.start_timer())
         return -1;
-    void *new_roots = no_storage ? nullptr : ctx->roots_ret2.p;
-    if (new_roots)
-        LAUNCH(ctx, k_fill_empty_roots, grid_for(max_na ? max_na : 1), BLOCK,
-               ctx->stream, (uint8_t *)new_roots, max_na ? max_na : 1);
-
-    DBuf map(ctx);
-    // small accounts-only deltas take the one-pass merge with lcp repair
-    // (closed-form ranks; O(delta) boundary lcps patched) — the scan-floor
-    // fix for the configs[4] shape. Everything else keeps the general
-    // overlay merge.
-    bool small = no_storage && n_acct > 0 && ctx->lcp_valid &&
-                 (n_acct <= (ctx->acct.n >> 6) ||
-                  (getenv("SRE_SD_FORCE") && n_acct <= ctx->acct.n));
-    bool st_closed_form = false;
-    if (small) {
-        if (apply_delta_small(ctx, acct_delta, n_acct, &map))
-            return -1;
-    } else {
-        // carry only when the pre-delta state HAS storage: while ns stays 0
-        // every retained root is EMPTY_ROOT (and accounts-only fast-path
-        // deltas may have drifted roots_ret's indexing — harmless, since
-        // it is then never read)
-        merge_io io;
-        io.map_out = &map;
-        if (new_roots && ctx->st.n > 0)
-            io.d_old_roots = (const uint8_t *)ctx->roots_ret.p;
-        io.d_new_roots = (uint8_t *)new_roots;
-        if (merge_delta(ctx, acct_delta, n_acct, st_delta, n_st, io))
-            return -1;
-        st_closed_form = io.st_closed_form;
-        ctx->lcp_valid = false; // recomputed below
-    }
-    // the merged state is adopted: the retained rows and storage roots
-    // describe the previous arrays until the end of this function refreshes
-    // them, so a failure from here on must leave retention disarmed
+    ctx->inc_cnt[0] = ctx->cap_count;
+    if (inc_merge(r))
+        return -1;
     ctx->cells_valid = false;
-    ctx->inc_cnt[3] = small;
-    ctx->inc_cnt[4] = st_closed_form;
-    uint64_t na = ctx->acct.n;
-    if (na == 0) {
+    ctx->inc_cnt[3] = r.small;
+    ctx->inc_cnt[4] = r.st_closed_form;
+    if (ctx->acct.n == 0) {
         invalidate_retention(ctx);
         memcpy(out_root, EMPTY_ROOT_H, 32);
         return 0;
     }
-
-    DBuf err(ctx), bitmap(ctx), dl(ctx), dls(ctx), recs(ctx),
-        depths(ctx), hist(ctx), roots(ctx), capcnt(ctx);
-    if (alloc_err_flag(ctx, err))
+    if (r.f.arm_err() || inc_mark_cells(r) || inc_touched_storage(r) ||
+        inc_seed_and_rehash(r) || inc_account_levels(r))
         return -1;
-    HIP_CHECK(ctx, bitmap.alloc(N_CELLS));
-    HIP_CHECK(ctx, hipMemsetAsync(bitmap.p, 0, N_CELLS, ctx->stream));
-    if (to_device(ctx, dl, acct_delta, n_acct))
-        return -1;
-    if (n_acct)
-        LAUNCH(ctx, k_mark_delta_cells, grid_for(n_acct), BLOCK, ctx->stream,
-               dl.as<sre_account_delta>(), n_acct, bitmap.as<uint8_t>());
-    if (n_st) {
-        if (to_device(ctx, dls, st_delta, n_st))
-            return -1;
-        LAUNCH(ctx, k_mark_delta_cells_st, grid_for(n_st), BLOCK, ctx->stream,
-               dls.as<sre_storage_entry>(), n_st, bitmap.as<uint8_t>());
-    }
-    pass_out po;
-    // recompute ONLY the touched accounts' storage tries: gather their
-    // merged segments into a compact array and run the storage machinery
-    // over it, scattering fresh roots over the carried ones
-    if (n_st) {
-        std::vector<key32> tkeys = storage_delta_accounts(st_delta, n_st);
-        uint32_t nt = (uint32_t)tkeys.size();
-        DBuf dtk(ctx), tlo(ctx), thi(ctx), taidx(ctx);
-        if (to_device(ctx, dtk, tkeys.data(), nt))
-            return -1;
-        HIP_CHECK(ctx, tlo.alloc((uint64_t)nt * 4));
-        HIP_CHECK(ctx, thi.alloc((uint64_t)nt * 4));
-        HIP_CHECK(ctx, taidx.alloc((uint64_t)nt * 4));
-        LAUNCH(ctx, k_touched_bounds, grid_for(nt), BLOCK, ctx->stream,
-               ctx->st.d, ctx->st.n, ctx->acct.d, na, dtk.as<uint8_t>(), nt,
-               tlo.as<uint32_t>(), thi.as<uint32_t>(), taidx.as<uint32_t>(),
-               (uint8_t *)new_roots, err.as<uint32_t>());
-        std::vector<uint32_t> lo, hi;
-        if (to_host(ctx, lo, tlo, nt) || to_host(ctx, hi, thi, nt))
-            return -1;
-        std::vector<uint32_t> offs = interval_offsets(lo, hi);
-        if (offs[nt] &&
-            run_storage_intervals(ctx, tlo.as<uint32_t>(), thi.as<uint32_t>(),
-                                  offs, (uint8_t *)new_roots, &po,
-                                  err.as<uint32_t>()))
-            return -1;
-        if (check_err(ctx, err.as<uint32_t>()))
-            return -1;
-    }
-    // lcp lives in the retained ping-pong buffer: the small path repaired
-    // it already; the general path recomputes it here (arming repair for
-    // the next delta)
-    if (!small) {
-        if (ctx->lcp_ret.grow(ctx, na + 1))
-            return -1;
-        LAUNCH(ctx, k_lcp_account, grid_for(na + 1), BLOCK, ctx->stream,
-               ctx->acct.d, na, 0, (int8_t *)ctx->lcp_ret.p, err.as<uint32_t>());
-        ctx->lcp_valid = true;
-    }
-    int8_t *lcp_p = (int8_t *)ctx->lcp_ret.p;
-    DBuf covered(ctx);
-    HIP_CHECK(ctx, recs.alloc(na * sizeof(node_rec)));
-    HIP_CHECK(ctx, depths.alloc(na));
-    HIP_CHECK(ctx, covered.alloc(na));
-    HIP_CHECK(ctx, hist.alloc(66 * 4));
-    HIP_CHECK(ctx, roots.alloc(32));
-    HIP_CHECK(ctx, hipMemsetAsync(depths.p, 0xFF, na, ctx->stream));
-    HIP_CHECK(ctx, hipMemsetAsync(covered.p, 0, na, ctx->stream));
-    HIP_CHECK(ctx, hipMemsetAsync(hist.p, 0, 66 * 4, ctx->stream));
-    DBuf abhash(ctx);
-    if (with_updates)
-        HIP_CHECK(ctx, abhash.alloc(na * 32));
-    // seed clean cell-tops; anything invalid dirties its cell
-    if (ctx->cap_count)
-        LAUNCH(ctx, k_revalidate_rows, grid_for(ctx->cap_count), BLOCK,
-               ctx->stream, (const cap_row *)ctx->cap_rows.p, ctx->cap_count,
-               map.as<uint32_t>(), lcp_p, bitmap.as<uint8_t>(),
-               recs.as<node_rec>(), depths.as<uint8_t>(), covered.as<uint8_t>(),
-               hist.as<uint32_t>(),
-               with_updates ? abhash.as<uint8_t>() : nullptr);
-    // rehash leaves of dirty cells and of positions no seed covers, with
-    // the carried+patched storage roots
-    EvTimer leaf;
-    HIP_CHECK(ctx, leaf.start(ctx->stream));
-    // compact the recompute set (covered == 0: dirty cells leave their
-    // positions uncovered, so this is exactly dirty ∪ uncovered) and
-    // launch the leaf kernel over it instead of sweeping all na lanes
-    uint32_t n_active = 0;
-    DBuf alist(ctx);
-    {
-        uint32_t nblk = grid_for(na);
-        DBuf ac(ctx), ao(ctx);
-        HIP_CHECK(ctx, ac.alloc((uint64_t)nblk * 4));
-        HIP_CHECK(ctx, ao.alloc((uint64_t)nblk * 4));
-        LAUNCH(ctx, k_active_hist, nblk, BLOCK, ctx->stream,
-               covered.as<uint8_t>(), na, ac.as<uint32_t>());
-        if (scan_u32(ctx, ac.as<uint32_t>(), ao.as<uint32_t>(), nblk,
-                     &n_active))
-            return -1;
-        HIP_CHECK(ctx, alist.alloc(((uint64_t)n_active ? n_active : 1) * 4));
-        LAUNCH(ctx, k_active_scatter, nblk, BLOCK, ctx->stream,
-               covered.as<uint8_t>(), na, ao.as<uint32_t>(),
-               alist.as<uint32_t>());
-    }
-    if (n_active)
-        LAUNCH(ctx, k_leaf_account, grid_for(n_active), BLOCK, ctx->stream,
-               ctx->acct.d, na,
-               (const uint8_t *)new_roots /* null=>EMPTY_ROOT */, lcp_p, 0,
-               recs.as<node_rec>(), depths.as<uint8_t>(), hist.as<uint32_t>(),
-               roots.as<uint8_t>(), nullptr, nullptr, nullptr, nullptr,
-               alist.as<uint32_t>(), n_active);
-    HIP_CHECK(ctx, leaf.stop(ctx->stream));
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    HIP_CHECK(ctx, leaf.ms(&ms));
-    po.leaf_ms += ms;
-    if (check_err(ctx, err.as<uint32_t>()))
-        return -1;
-    // final dirty-cell set (incl. revalidation misses)
-    if (bitmap_out && to_host(ctx, *bitmap_out, bitmap, N_CELLS))
-        return -1;
-    uint32_t hist_host[66];
-    HIP_CHECK(ctx, hipMemcpy(hist_host, hist.p, 66 * 4, hipMemcpyDeviceToHost));
-    // every rehashed leaf (k_leaf_account) and every seeded row
-    // (k_revalidate_rows) adds exactly one to hist
-    uint64_t level_inputs = 0;
-    for (int d = 0; d < 66; ++d)
-        level_inputs += hist_host[d];
-    ctx->inc_cnt[1] = level_inputs - n_active;
-    ctx->inc_cnt[2] = n_active;
-    // fresh capture for the next delta; the retained rows were consumed by
-    // k_revalidate_rows above, so capturing over the same buffer is safe —
-    // unless na grew past its capacity, in which case swap in a bigger one.
-    if (ctx->cap_rows.grow(ctx, cap_rows_for(na), sizeof(cap_row)))
-        return -1;
-    HIP_CHECK(ctx, capcnt.alloc(4));
-    HIP_CHECK(ctx, hipMemsetAsync(capcnt.p, 0, 4, ctx->stream));
-    size_t upd_start = ctx->updates.size();
-    level_in in;
-    in.n = na;
-    in.recs = recs.as<node_rec>();
-    in.depths = depths.as<uint8_t>();
-    in.lcp = lcp_p;
-    in.keys = (const uint8_t *)ctx->acct.d + offsetof(sre_account_entry, key);
-    in.key_stride = sizeof(sre_account_entry);
-    in.hist_host = hist_host;
-    in.seg_roots = roots.as<uint8_t>();
-    in.err = err.as<uint32_t>();
-    in.updates_kind = with_updates ? 0 : -1;
-    in.bhash = with_updates ? abhash.as<uint8_t>() : nullptr;
-    cell_capture cap;
-    cap.depth = CELL_NIBBLES;
-    cap.rows = (cap_row *)ctx->cap_rows.p;
-    cap.count = capcnt.as<uint32_t>();
-    cap.capacity = ctx->cap_rows.cap;
-    if (run_levels(ctx, in, &po, cap))
-        return -1;
-    if (with_updates) // account rows carry no acct_key; clear the seg stash
-        for (size_t r = upd_start; r < ctx->updates.size(); ++r)
-            memset(ctx->updates[r].pad_, 0, sizeof(ctx->updates[r].pad_));
-    if (check_err(ctx, err.as<uint32_t>()))
-        return -1;
-    uint32_t cnt = 0;
-    HIP_CHECK(ctx, hipMemcpy(&cnt, capcnt.p, 4, hipMemcpyDeviceToHost));
-    ctx->cap_count = cnt;
-    ctx->inc_cnt[5] = cnt;
-    // swap the ping-pong retained roots (chained deltas)
-    if (!no_storage)
+    // commit: the ping-pong partner holds the post-delta storage roots
+    if (!r.no_storage)
         std::swap(ctx->roots_ret, ctx->roots_ret2);
     ctx->cells_valid = true;
-
-    HIP_CHECK(ctx, whole.stop(ctx->stream));
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    float total_ms = 0;
-    HIP_CHECK(ctx, whole.ms(&total_ms));
     // po counts only the subset storage leaves, not the account leaves
-    // re-hashed above: the leaf/block totals would be partial numbers, so
-    // they are published as zero
-    po.leaf_count = po.leaf_blocks = po.branch_blocks = 0;
-    publish_stats(ctx, po, total_ms);
-
-    HIP_CHECK(ctx, hipMemcpy(out_root, roots.p, 32, hipMemcpyDeviceToHost));
+    // rehashed in step 4: the leaf/block totals would be partial numbers,
+    // so they are published as zero
+    r.f.po.leaf_count = r.f.po.leaf_blocks = r.f.po.branch_blocks = 0;
+    if (r.f.publish())
+        return -1;
+    HIP_CHECK(ctx, hipMemcpy(out_root, r.roots.p, 32, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -5818,7 +5829,7 @@ extern "C" int sre_incremental_root(sre_ctx *ctx,
     // can no longer seed future update emission
     ctx->snap_valid = false;
     return incremental_root_impl(ctx, acct_delta, n_acct, st_delta, n_st,
-                                 out_root, false, nullptr);
+                                 out_root, nullptr);
 }
 
 extern "C" int sre_root_retaining_with_updates(sre_ctx *ctx,
@@ -5858,7 +5869,7 @@ extern "C" int sre_incremental_root_with_updates(
     ctx->updates.clear();
     std::vector<uint8_t> bitmap;
     int rc = incremental_root_impl(ctx, acct_delta, n_acct, st_delta, n_st,
-                                   out_root, true, &bitmap);
+                                   out_root, &bitmap);
     ctx->retain_updates = false;
     if (rc) {
         ctx->updates.clear(); // no partial emission stays readable
@@ -5901,11 +5912,12 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
                                    const sre_storage_entry *st_delta,
                                    uint64_t n_st, uint8_t out_root[32])
 {
-    if (begin_call(ctx, true))
+    root_call f{ctx};
+    if (f.begin(true))
         return -1;
     invalidate_retention(ctx);
-    EvTimer whole;
-    HIP_CHECK(ctx, whole.start(ctx->stream));
+    if (f.start_timer())
+        return -1;
 
     // supplied storage roots: kind-1 path-[] rows with root_hash
     std::vector<std::array<uint8_t, 64>> kv; // key || root
@@ -5935,27 +5947,20 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
     if (merge_delta(ctx, acct_delta, n_acct, st_delta, n_st, io))
         return -1;
     uint64_t na = ctx->acct.n, ns = ctx->st.n;
-    if (na == 0) {
-        if (ns != 0) {
-            set_err(ctx, "storage entries without accounts");
-            return -1;
-        }
-        memcpy(out_root, EMPTY_ROOT_H, 32);
-        return 0;
-    }
+    if (na == 0)
+        return empty_state_root(ctx, out_root);
 
-    DBuf err(ctx), acct_roots(ctx), roots(ctx);
-    if (alloc_err_flag(ctx, err))
+    DBuf acct_roots(ctx), roots(ctx);
+    if (f.arm_err())
         return -1;
     HIP_CHECK(ctx, acct_roots.alloc(na * 32));
     HIP_CHECK(ctx, roots.alloc(32));
     LAUNCH(ctx, k_fill_empty_roots, grid_for(na), BLOCK, ctx->stream,
            acct_roots.as<uint8_t>(), na);
-    pass_out po;
     if (ns) {
         // segment the resident storage; seed supplied roots / flag rebuilds
         storage_segs sg(ctx);
-        if (segment_storage(ctx, ctx->st.d, ns, err.as<uint32_t>(), sg))
+        if (segment_storage(ctx, ctx->st.d, ns, f.flag(), sg))
             return -1;
         const uint32_t n_seg = sg.n_seg;
         DBuf need(ctx), dkv(ctx), dtk(ctx);
@@ -5981,24 +5986,18 @@ extern "C" int sre_root_from_nodes(sre_ctx *ctx,
                 return -1;
             if (run_storage_intervals(ctx, dlo.as<uint32_t>(),
                                       dhi.as<uint32_t>(), offs,
-                                      acct_roots.as<uint8_t>(), &po,
-                                      err.as<uint32_t>()))
+                                      acct_roots.as<uint8_t>(), &f.po,
+                                      f.flag()))
                 return -1;
         }
-        if (check_err(ctx, err.as<uint32_t>()))
+        if (check_err(ctx, f.flag()))
             return -1;
     }
     if (run_account_pass(ctx, acct_roots.as<uint8_t>(), 0,
-                         roots.as<uint8_t>(), nullptr, nullptr, &po,
-                         err.as<uint32_t>()))
+                         roots.as<uint8_t>(), nullptr, nullptr, &f.po,
+                         f.flag()) ||
+        f.finish())
         return -1;
-    if (check_err(ctx, err.as<uint32_t>()))
-        return -1;
-    HIP_CHECK(ctx, whole.stop(ctx->stream));
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    float total_ms = 0;
-    HIP_CHECK(ctx, whole.ms(&total_ms));
-    publish_stats(ctx, po, total_ms);
     HIP_CHECK(ctx, hipMemcpy(out_root, roots.p, 32, hipMemcpyDeviceToHost));
     return 0;
 }

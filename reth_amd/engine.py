@@ -107,6 +107,46 @@ def build(verbose=False):
         print(f"built {LIB}")
 
 
+_P, _U64, _U32, _INT = (ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                        ctypes.c_int)
+_DELTA = [_P, _P, _U64, _P, _U64]  # ctx, account rows, n, storage rows, n
+
+# Every entry point of include/sre.h, grouped by (restype, argtypes); lib()
+# applies them, so no call site converts an argument by hand. Scalars map by
+# C type (uint64_t, uint32_t, int); every pointer or array parameter is
+# c_void_p, which takes numpy pointers, None, ctypes arrays and byref
+# objects. tests/test_abi_cpu.py checks the table against the header.
+_SIGNATURES = (
+    (_P, [_INT], "sre_create"),
+    (None, [_P], "sre_destroy"),
+    (ctypes.c_char_p, [_P], "sre_last_error"),
+    (ctypes.c_int64, [_P], "sre_updates_count"),
+    (_INT, [_P, _INT], "sre_set_revert_capture"),
+    (_INT, [_P, _P],  # ctx, one output
+     "sre_root sre_root_with_updates sre_root_retaining "
+     "sre_root_retaining_with_updates sre_unwind sre_unwind_with_updates "
+     "sre_get_stats sre_get_path_counters sre_get_incremental_counters "
+     "sre_get_hash_sort_counters sre_get_revert_counters"),
+    (_INT, [_P, _P, _P], "sre_resident_counts sre_revert_counts"),
+    (_INT, [_P, _P, _U64],  # ctx, rows, count
+     "sre_upload_accounts sre_upload_storage sre_set_accounts_device "
+     "sre_set_storage_device sre_download_accounts sre_download_storage "
+     "sre_updates_get sre_storage_roots"),
+    (_INT, _DELTA, "sre_upload_plain_state sre_set_plain_state_device "
+                   "sre_apply_delta sre_revert_get"),
+    (_INT, _DELTA + [_P],
+     "sre_incremental_root sre_incremental_root_with_updates"),
+    (_INT, [_P, _P, _U64, _P, _U64, _P, _U64, _P],
+     "sre_root_from_nodes sre_account_proof"),
+    (_INT, [_P, _P, _P, _U64, _P, _P, _U64, _P, _U64, _P], "sre_storage_proof"),
+    (_INT, [_P, _P, _U64, _U32, _U64, _P],
+     "sre_keccak_batch_device sre_keccak_long_device"),
+    (_INT, [_P] * 5, "sre_subtree_roots"),
+    (_INT, [_P] * 6, "sre_finish_top"),
+)
+ABI = {name: (restype, argtypes) for restype, argtypes, names in _SIGNATURES
+       for name in names.split()}
+
 _lib = None
 
 
@@ -117,13 +157,9 @@ def lib():
             raise RuntimeError(
                 f"{LIB} missing — run __graft_entry__.build() / reth_amd.engine.build()")
         _lib = ctypes.CDLL(LIB)
-        _lib.sre_create.restype = ctypes.c_void_p
-        _lib.sre_create.argtypes = [ctypes.c_int]
-        _lib.sre_last_error.restype = ctypes.c_char_p
-        _lib.sre_last_error.argtypes = [ctypes.c_void_p]
-        _lib.sre_destroy.argtypes = [ctypes.c_void_p]
-        _lib.sre_updates_count.restype = ctypes.c_int64
-        _lib.sre_updates_count.argtypes = [ctypes.c_void_p]
+        for name, (restype, argtypes) in ABI.items():
+            fn = getattr(_lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     return _lib
 
 
@@ -155,16 +191,22 @@ class StateRootEngine:
 
     def _check(self, rc):
         if rc != 0:
-            raise RuntimeError(self._lib.sre_last_error(
-                ctypes.c_void_p(self._ctx)).decode())
+            raise RuntimeError(self._lib.sre_last_error(self._ctx).decode())
+
+    def _root(self, fn, *args):
+        """Call a root-type entry point: its arguments, then the 32-byte
+        output root, which is returned."""
+        out = (ctypes.c_uint8 * 32)()
+        self._check(fn(self._ctx, *args, out))
+        return bytes(out)
 
     # ---- input upload ----
     def upload(self, accounts: np.ndarray, storage: np.ndarray):
         assert accounts.dtype == ACCOUNT_DTYPE and storage.dtype == STORAGE_DTYPE
         self._check(self._lib.sre_upload_accounts(
-            ctypes.c_void_p(self._ctx), _np_ptr(accounts), len(accounts)))
+            self._ctx, _np_ptr(accounts), len(accounts)))
         self._check(self._lib.sre_upload_storage(
-            ctypes.c_void_p(self._ctx), _np_ptr(storage), len(storage)))
+            self._ctx, _np_ptr(storage), len(storage)))
 
     def set_device_tensors(self, acct_u8, st_u8):
         """Borrow torch GPU tensors: acct (na,104) uint8, st (ns,96) uint8,
@@ -174,11 +216,9 @@ class StateRootEngine:
         assert acct_u8.shape[1] == 104 and st_u8.shape[1] == 96
         self._keep = [acct_u8, st_u8]
         self._check(self._lib.sre_set_accounts_device(
-            ctypes.c_void_p(self._ctx), ctypes.c_void_p(acct_u8.data_ptr()),
-            acct_u8.shape[0]))
+            self._ctx, acct_u8.data_ptr(), acct_u8.shape[0]))
         self._check(self._lib.sre_set_storage_device(
-            ctypes.c_void_p(self._ctx), ctypes.c_void_p(st_u8.data_ptr()),
-            st_u8.shape[0]))
+            self._ctx, st_u8.data_ptr(), st_u8.shape[0]))
 
     def upload_plain(self, accounts: np.ndarray, storage: np.ndarray):
         """Replace the resident state by the hashed, sorted form of plain
@@ -190,9 +230,8 @@ class StateRootEngine:
         accounts = np.ascontiguousarray(accounts)
         storage = np.ascontiguousarray(storage)
         self._check(self._lib.sre_upload_plain_state(
-            ctypes.c_void_p(self._ctx), _np_ptr(accounts),
-            ctypes.c_uint64(len(accounts)), _np_ptr(storage),
-            ctypes.c_uint64(len(storage))))
+            self._ctx, _np_ptr(accounts), len(accounts), _np_ptr(storage),
+            len(storage)))
         self._keep = []  # the new state is engine-owned
 
     def set_plain_device_tensors(self, acct_u8, st_u8):
@@ -209,18 +248,17 @@ class StateRootEngine:
             torch.cuda.synchronize(acct_u8.device)
         na, ns = acct_u8.shape[0], st_u8.shape[0]
         self._check(self._lib.sre_set_plain_state_device(
-            ctypes.c_void_p(self._ctx),
-            ctypes.c_void_p(acct_u8.data_ptr() if na else None),
-            ctypes.c_uint64(na),
-            ctypes.c_void_p(st_u8.data_ptr() if ns else None),
-            ctypes.c_uint64(ns)))
+            self._ctx, acct_u8.data_ptr() if na else None, na,
+            st_u8.data_ptr() if ns else None, ns))
         self._keep = []
 
-    def resident_counts(self):
+    def _counts(self, fn):
         na, ns = ctypes.c_uint64(), ctypes.c_uint64()
-        self._check(self._lib.sre_resident_counts(
-            ctypes.c_void_p(self._ctx), ctypes.byref(na), ctypes.byref(ns)))
+        self._check(fn(self._ctx, ctypes.byref(na), ctypes.byref(ns)))
         return na.value, ns.value
+
+    def resident_counts(self):
+        return self._counts(self._lib.sre_resident_counts)
 
     def download(self):
         """The resident state as (ACCOUNT_DTYPE array, STORAGE_DTYPE array):
@@ -229,17 +267,15 @@ class StateRootEngine:
         acct = np.zeros(na, dtype=ACCOUNT_DTYPE)
         st = np.zeros(ns, dtype=STORAGE_DTYPE)
         self._check(self._lib.sre_download_accounts(
-            ctypes.c_void_p(self._ctx), _np_ptr(acct), ctypes.c_uint64(na)))
-        self._check(self._lib.sre_download_storage(
-            ctypes.c_void_p(self._ctx), _np_ptr(st), ctypes.c_uint64(ns)))
+            self._ctx, _np_ptr(acct), na))
+        self._check(self._lib.sre_download_storage(self._ctx, _np_ptr(st), ns))
         return acct, st
 
     def hash_sort_counters(self) -> dict:
         """What the last plain upload did (include/sre.h
         sre_get_hash_sort_counters)."""
         out = (ctypes.c_uint64 * 6)()
-        self._check(self._lib.sre_get_hash_sort_counters(
-            ctypes.c_void_p(self._ctx), out))
+        self._check(self._lib.sre_get_hash_sort_counters(self._ctx, out))
         return {"keccak_f": out[0], "passes": out[1], "skipped": out[2],
                 "tie_rows": out[3], "tie_runs": out[4], "addr_reused": out[5]}
 
@@ -260,8 +296,8 @@ class StateRootEngine:
         assert acct_delta.dtype == DELTA_DTYPE
         assert st_delta.dtype == STORAGE_DTYPE
         self._check(self._lib.sre_apply_delta(
-            ctypes.c_void_p(self._ctx), _np_ptr(acct_delta), len(acct_delta),
-            _np_ptr(st_delta), len(st_delta)))
+            self._ctx, _np_ptr(acct_delta), len(acct_delta), _np_ptr(st_delta),
+            len(st_delta)))
 
     # ---- compute ----
     def root_retaining(self) -> bytes:
@@ -269,10 +305,7 @@ class StateRootEngine:
         account's storage root, so following incremental_root() calls
         recompute only what a delta touches. See include/sre.h
         sre_root_retaining."""
-        out = (ctypes.c_uint8 * 32)()
-        self._check(self._lib.sre_root_retaining(
-            ctypes.c_void_p(self._ctx), out))
-        return bytes(out)
+        return self._root(self._lib.sre_root_retaining)
 
     def incremental_root(self, acct_delta: np.ndarray,
                          st_delta: np.ndarray = None) -> bytes:
@@ -287,23 +320,18 @@ class StateRootEngine:
         if st_delta is None:
             st_delta = np.zeros(0, dtype=STORAGE_DTYPE)
         assert st_delta.dtype == STORAGE_DTYPE
-        out = (ctypes.c_uint8 * 32)()
-        self._check(self._lib.sre_incremental_root(
-            ctypes.c_void_p(self._ctx), _np_ptr(acct_delta),
-            len(acct_delta), _np_ptr(st_delta), len(st_delta), out))
-        return bytes(out)
+        return self._root(self._lib.sre_incremental_root,
+                          _np_ptr(acct_delta), len(acct_delta),
+                          _np_ptr(st_delta), len(st_delta))
 
     def root(self) -> bytes:
-        out = (ctypes.c_uint8 * 32)()
-        self._check(self._lib.sre_root(ctypes.c_void_p(self._ctx), out))
-        return bytes(out)
+        return self._root(self._lib.sre_root)
 
     def _fetch_updates(self):
-        n = self._lib.sre_updates_count(ctypes.c_void_p(self._ctx))
+        n = self._lib.sre_updates_count(self._ctx)
         rows = np.zeros(n, dtype=UPDATE_DTYPE)
         if n:
-            self._check(self._lib.sre_updates_get(
-                ctypes.c_void_p(self._ctx), _np_ptr(rows), n))
+            self._check(self._lib.sre_updates_get(self._ctx, _np_ptr(rows), n))
         return rows
 
     def root_retaining_with_updates(self):
@@ -311,10 +339,8 @@ class StateRootEngine:
         retention and the stored-row snapshot so following
         incremental_root_with_updates calls emit net row diffs
         (include/sre.h sre_root_retaining_with_updates)."""
-        out = (ctypes.c_uint8 * 32)()
-        self._check(self._lib.sre_root_retaining_with_updates(
-            ctypes.c_void_p(self._ctx), out))
-        return bytes(out), self._fetch_updates()
+        root = self._root(self._lib.sre_root_retaining_with_updates)
+        return root, self._fetch_updates()
 
     def incremental_root_with_updates(self, acct_delta: np.ndarray,
                                       st_delta: np.ndarray = None):
@@ -329,12 +355,10 @@ class StateRootEngine:
         if st_delta is None:
             st_delta = np.zeros(0, dtype=STORAGE_DTYPE)
         assert st_delta.dtype == STORAGE_DTYPE
-        out = (ctypes.c_uint8 * 32)()
-        self._check(self._lib.sre_incremental_root_with_updates(
-            ctypes.c_void_p(self._ctx), _np_ptr(acct_delta),
-            ctypes.c_uint64(len(acct_delta)), _np_ptr(st_delta),
-            ctypes.c_uint64(len(st_delta)), out))
-        return bytes(out), self._fetch_updates()
+        root = self._root(self._lib.sre_incremental_root_with_updates,
+                          _np_ptr(acct_delta), len(acct_delta),
+                          _np_ptr(st_delta), len(st_delta))
+        return root, self._fetch_updates()
 
     def root_from_nodes(self, rows: np.ndarray, acct_delta: np.ndarray = None,
                         st_delta: np.ndarray = None) -> bytes:
@@ -351,24 +375,17 @@ class StateRootEngine:
             st_delta = np.zeros(0, dtype=STORAGE_DTYPE)
         assert acct_delta.dtype == DELTA_DTYPE
         assert st_delta.dtype == STORAGE_DTYPE
-        out = (ctypes.c_uint8 * 32)()
-        # 8 args: stack-passed lengths MUST be explicit c_uint64 (a bare
-        # int becomes a 32-bit stack slot with a garbage upper half)
-        self._check(self._lib.sre_root_from_nodes(
-            ctypes.c_void_p(self._ctx), _np_ptr(rows),
-            ctypes.c_uint64(len(rows)),
-            _np_ptr(acct_delta), ctypes.c_uint64(len(acct_delta)),
-            _np_ptr(st_delta), ctypes.c_uint64(len(st_delta)), out))
-        return bytes(out)
+        return self._root(self._lib.sre_root_from_nodes,
+                          _np_ptr(rows), len(rows),
+                          _np_ptr(acct_delta), len(acct_delta),
+                          _np_ptr(st_delta), len(st_delta))
 
     def root_with_updates(self):
         """State root + TrieUpdates rows (UPDATE_DTYPE), sorted like reth's
         TrieUpdates::into_sorted. Surface of
         StateRootProvider::state_root_with_updates."""
-        out = (ctypes.c_uint8 * 32)()
-        self._check(self._lib.sre_root_with_updates(
-            ctypes.c_void_p(self._ctx), out))
-        return bytes(out), self._fetch_updates()
+        root = self._root(self._lib.sre_root_with_updates)
+        return root, self._fetch_updates()
 
     def account_proof(self, targets, cap_nodes=None, cap_lens=None) -> list:
         """Account multiproof: per target, the proof node RLPs root-first
@@ -412,10 +429,9 @@ class StateRootEngine:
         lens = np.zeros(cap_lens, dtype=np.uint32)
         counts = np.zeros(n, dtype=np.uint32)
         self._check(fn(
-            ctypes.c_void_p(self._ctx), *[_np_ptr(k) for k in keys],
-            ctypes.c_uint64(n), *[_np_ptr(o) for o in extra_out],
-            _np_ptr(nodes), ctypes.c_uint64(cap_nodes),
-            _np_ptr(lens), ctypes.c_uint64(cap_lens), _np_ptr(counts)))
+            self._ctx, *[_np_ptr(k) for k in keys], n,
+            *[_np_ptr(o) for o in extra_out], _np_ptr(nodes), cap_nodes,
+            _np_ptr(lens), cap_lens, _np_ptr(counts)))
         out, off, li = [], 0, 0
         for cnt in counts:
             tl = []
@@ -428,8 +444,7 @@ class StateRootEngine:
 
     def storage_roots(self, n) -> np.ndarray:
         out = np.empty((n, 32), dtype=np.uint8)
-        self._check(self._lib.sre_storage_roots(
-            ctypes.c_void_p(self._ctx), _np_ptr(out), n))
+        self._check(self._lib.sre_storage_roots(self._ctx, _np_ptr(out), n))
         return out
 
     def subtree_roots(self):
@@ -438,19 +453,17 @@ class StateRootEngine:
         roots = np.zeros((16, 32), dtype=np.uint8)
         counts = np.zeros(16, dtype=np.uint64)
         self._check(self._lib.sre_subtree_roots(
-            ctypes.c_void_p(self._ctx), _np_ptr(refs), _np_ptr(lens),
-            _np_ptr(roots), _np_ptr(counts)))
+            self._ctx, _np_ptr(refs), _np_ptr(lens), _np_ptr(roots),
+            _np_ptr(counts)))
         return refs, lens, roots, counts
 
     def finish_top(self, refs, lens, roots, counts) -> bytes:
-        out = (ctypes.c_uint8 * 32)()
-        self._check(self._lib.sre_finish_top(
-            ctypes.c_void_p(self._ctx),
+        return self._root(
+            self._lib.sre_finish_top,
             _np_ptr(np.ascontiguousarray(refs, dtype=np.uint8)),
             _np_ptr(np.ascontiguousarray(lens, dtype=np.uint8)),
             _np_ptr(np.ascontiguousarray(roots, dtype=np.uint8)),
-            _np_ptr(np.ascontiguousarray(counts, dtype=np.uint64)), out))
-        return bytes(out)
+            _np_ptr(np.ascontiguousarray(counts, dtype=np.uint64)))
 
     def keccak_batch_device(self, in_tensor, msg_len, out_tensor):
         """Hash n messages of msg_len bytes at a fixed stride (device memory).
@@ -475,23 +488,20 @@ class StateRootEngine:
             torch.cuda.synchronize(in_tensor.device)
         n, stride = in_tensor.shape
         self._check(fn(
-            ctypes.c_void_p(self._ctx), ctypes.c_void_p(in_tensor.data_ptr()),
-            ctypes.c_uint64(stride), ctypes.c_uint32(msg_len), ctypes.c_uint64(n),
-            ctypes.c_void_p(out_tensor.data_ptr())))
+            self._ctx, in_tensor.data_ptr(), stride, msg_len, n,
+            out_tensor.data_ptr()))
         return out_tensor
 
     def stats(self) -> dict:
         s = SreStats()
-        self._check(self._lib.sre_get_stats(ctypes.c_void_p(self._ctx),
-                                            ctypes.byref(s)))
+        self._check(self._lib.sre_get_stats(self._ctx, ctypes.byref(s)))
         return {f[0]: getattr(s, f[0]) for f in SreStats._fields_}
 
     def path_counters(self) -> dict:
         """Which branch-pipeline paths the last root-type call took
         (include/sre.h sre_get_path_counters)."""
         out = (ctypes.c_uint64 * 4)()
-        self._check(self._lib.sre_get_path_counters(
-            ctypes.c_void_p(self._ctx), out))
+        self._check(self._lib.sre_get_path_counters(self._ctx, out))
         return {"class_levels": out[0], "fused_groups": out[1],
                 "chunks": out[2], "pipe2_levels": out[3]}
 
@@ -500,8 +510,7 @@ class StateRootEngine:
         call reused and recomputed (include/sre.h
         sre_get_incremental_counters)."""
         out = (ctypes.c_uint64 * 6)()
-        self._check(self._lib.sre_get_incremental_counters(
-            ctypes.c_void_p(self._ctx), out))
+        self._check(self._lib.sre_get_incremental_counters(self._ctx, out))
         return {"examined": out[0], "seeded": out[1], "rehashed": out[2],
                 "small_acct_merge": out[3], "small_st_merge": out[4],
                 "captured": out[5]}
@@ -514,15 +523,12 @@ class StateRootEngine:
         delta that undoes it (include/sre.h sre_set_revert_capture); only
         the last one is kept. Turning it off drops the stored revert."""
         self._check(self._lib.sre_set_revert_capture(
-            ctypes.c_void_p(self._ctx), ctypes.c_int(1 if on else 0)))
+            self._ctx, 1 if on else 0))
 
     def revert_counts(self):
         """(account rows, storage rows) of the stored revert; (0, 0) when
         none is stored."""
-        na, ns = ctypes.c_uint64(), ctypes.c_uint64()
-        self._check(self._lib.sre_revert_counts(
-            ctypes.c_void_p(self._ctx), ctypes.byref(na), ctypes.byref(ns)))
-        return na.value, ns.value
+        return self._counts(self._lib.sre_revert_counts)
 
     def revert(self):
         """The stored revert as (DELTA_DTYPE array, STORAGE_DTYPE array): a
@@ -534,8 +540,7 @@ class StateRootEngine:
         acct = np.zeros(na, dtype=DELTA_DTYPE)
         st = np.zeros(ns, dtype=STORAGE_DTYPE)
         self._check(self._lib.sre_revert_get(
-            ctypes.c_void_p(self._ctx), _np_ptr(acct), ctypes.c_uint64(na),
-            _np_ptr(st), ctypes.c_uint64(ns)))
+            self._ctx, _np_ptr(acct), na, _np_ptr(st), ns))
         return acct, st
 
     def unwind(self) -> bytes:
@@ -543,23 +548,18 @@ class StateRootEngine:
         the root go back to before the last captured delta (the unwind of
         MerkleStage). With capture on, the stored revert becomes the redo.
         Raises with `no-revert-captured` when nothing is stored."""
-        out = (ctypes.c_uint8 * 32)()
-        self._check(self._lib.sre_unwind(ctypes.c_void_p(self._ctx), out))
-        return bytes(out)
+        return self._root(self._lib.sre_unwind)
 
     def unwind_with_updates(self):
         """incremental_root_with_updates over the stored revert: (root, net
         row diff against the trie before the unwind)."""
-        out = (ctypes.c_uint8 * 32)()
-        self._check(self._lib.sre_unwind_with_updates(
-            ctypes.c_void_p(self._ctx), out))
-        return bytes(out), self._fetch_updates()
+        root = self._root(self._lib.sre_unwind_with_updates)
+        return root, self._fetch_updates()
 
     def revert_counters(self) -> dict:
         """What the last revert capture did (include/sre.h
         sre_get_revert_counters)."""
         out = (ctypes.c_uint64 * 4)()
-        self._check(self._lib.sre_get_revert_counters(
-            ctypes.c_void_p(self._ctx), out))
+        self._check(self._lib.sre_get_revert_counters(self._ctx, out))
         return {"acct_rows": out[0], "st_rows": out[1], "wiped_rows": out[2],
                 "no_row": out[3]}

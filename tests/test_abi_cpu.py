@@ -58,3 +58,47 @@ def test_struct_sizes_match_header_contract():
     assert STORAGE_DTYPE.itemsize == 96
     assert DELTA_DTYPE.itemsize == 112
     assert UPDATE_DTYPE.itemsize == 624
+
+
+def _declarations():
+    """{name: (return type, [parameter, ...])} parsed from the header."""
+    text = open(HDR).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    decls = {}
+    for m in re.finditer(
+            r"^([A-Za-z_][\w \t]*?[\s\*]+)(sre_\w+)\s*\(([^;{}]*?)\)\s*;",
+            text, flags=re.M | re.S):
+        params = [" ".join(p.split()) for p in m.group(3).split(",")]
+        assert m.group(2) not in decls, m.group(2)
+        decls[m.group(2)] = (" ".join(m.group(1).split()), params)
+    return decls
+
+
+def _param_kind(param):
+    if "*" in param or "[" in param:
+        return ctypes.c_void_p
+    return {"uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
+            "int": ctypes.c_int}[param.rsplit(" ", 1)[0]]
+
+
+_RET_KIND = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "void": None,
+             "const char *": ctypes.c_char_p, "sre_ctx *": ctypes.c_void_p}
+
+
+def test_declaration_parse_finds_the_symbol_set():
+    decls = _declarations()
+    assert sorted(decls) == _declared_symbols()
+    assert len(decls) == 39
+
+
+def test_binding_table_matches_header():
+    from reth_amd.engine import ABI
+    decls = _declarations()
+    assert sorted(ABI) == sorted(decls)
+    for name, (ret, params) in decls.items():
+        restype, argtypes = ABI[name]
+        assert restype is _RET_KIND[ret], name
+        assert len(argtypes) == len(params), name
+        for i, (got, param) in enumerate(zip(argtypes, params)):
+            assert got is _param_kind(param), (name, i, param)
