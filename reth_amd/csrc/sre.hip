@@ -341,7 +341,9 @@ __device__ __forceinline__ int min_be_len(const uint8_t *v)
 // active trie node record, 48 bytes
 struct __attribute__((aligned(16))) node_rec {
     uint32_t s, e;    // covered leaf interval [s, e)
-    uint32_t seg;     // segment id (storage: account segment; account: 0/top nibble)
+    uint32_t seg;     // key word: the big-endian first four bytes of key[s], so
+                      // nibble p < 8 is (seg >> (28 - 4p)) & 0xF, the account
+                      // shard seg >> 28, the capture cell seg >> 12
     int8_t depth;     // parent branch depth this node waits for (-1 = root)
     uint8_t ref_len;  // 1..33 (0 marks a consumed root record)
     uint8_t ref[33];
@@ -358,6 +360,12 @@ __device__ __forceinline__ void copy_rec(node_rec *dst, const node_rec *src)
 #pragma unroll
     for (int i = 0; i < 3; ++i)
         d4[i] = s4[i];
+}
+
+__device__ __forceinline__ uint32_t key_word(const uint8_t *key)
+{
+    return ((uint32_t)key[0] << 24) | ((uint32_t)key[1] << 16) |
+           ((uint32_t)key[2] << 8) | (uint32_t)key[3];
 }
 
 // ref from an LDS-resident rlp + its precomputed hash
@@ -582,8 +590,9 @@ __global__ void k_lcp_account(const sre_account_entry *__restrict__ acct, uint64
 // junction on either side flags it and, like a zero-valued slot, writes
 // neither record nor depth byte (a duplicate key's 64 shared nibbles would
 // put `from` at 65); the host checks err before any level runs.
-// Records carry seg = 0: segment ids exist only after this kernel (scan of
-// the flags) and are looked up per entry where they are consumed.
+// Records carry the key word in seg, not a segment id: the ids exist only
+// after this kernel (scan of the flags) and are looked up per entry where
+// they are consumed.
 #define SLOT_STO 136
 __device__ __forceinline__ void words_of(uint4 a, uint4 b, uint64_t w[4])
 {
@@ -781,7 +790,7 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
                 uint32_t w[12];
                 w[0] = (uint32_t)i;
                 w[1] = (uint32_t)(i + 1);
-                w[2] = 0;
+                w[2] = __builtin_bswap32((uint32_t)K[0]); // key word
                 w[3] = (uint32_t)(uint8_t)(int8_t)D | (33u << 8) |
                        (0xa0u << 16) | ((uint32_t)(s[0] & 0xFF) << 24);
                 w[4] = (uint32_t)(s[0] >> 8);
@@ -802,7 +811,7 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
                 node_rec *r = &recs[i];
                 r->s = (uint32_t)i;
                 r->e = (uint32_t)(i + 1);
-                r->seg = 0;
+                r->seg = key_word(key);
                 r->depth = (int8_t)D;
                 r->ref_len = (uint8_t)len;
                 uint64_t mm[4] = {m0, m1, m2, m3};
@@ -842,7 +851,7 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_storage(
             node_rec *r = &recs[i];
             r->s = (uint32_t)i;
             r->e = (uint32_t)(i + 1);
-            r->seg = 0;
+            r->seg = key_word(key);
             r->depth = (int8_t)D;
             uint8_t rl;
             make_ref(slot, len, hash, r->ref, &rl);
@@ -965,7 +974,8 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_account(
         node_rec r;
         r.s = (uint32_t)i;
         r.e = (uint32_t)(i + 1);
-        r.seg = subtree ? (uint32_t)(key[0] >> 4) : 0u;
+        r.seg = key_word(key);
+        const uint32_t shard = subtree ? r.seg >> 28 : 0u;
         r.depth = (int8_t)D;
         make_ref(slot, len, hash, r.ref, &r.ref_len);
         r.pad_ = D >= 0 ? nib_of(key, D) : 0;
@@ -977,11 +987,11 @@ __global__ void __launch_bounds__(BLOCK) k_leaf_account(
                 uint64_t chash[4];
                 int clen = emit(1, chash); // child-of-root-branch form
                 uint8_t clens;
-                make_ref(slot, clen, chash, child_refs + 33ull * r.seg, &clens);
-                child_lens[r.seg] = clens;
+                make_ref(slot, clen, chash, child_refs + 33ull * shard, &clens);
+                child_lens[shard] = clens;
                 len = emit(0, hash); // standalone-root form
             }
-            memcpy(roots + 32ull * r.seg, hash, 32);
+            memcpy(roots + 32ull * shard, hash, 32);
         }
     } // active
     __syncthreads();
@@ -1502,17 +1512,110 @@ __global__ void __launch_bounds__(BLOCK_A, 8) k_branch_assemble(
 // scratch of >= SLOT_EXT bytes (may alias the message slot: the inline
 // words are consumed before the first wrap reuses it).
 #define SLOT_EXT 88
+// hist_l of the branch kernels: [0..65] the pending bumps, [BR_HIST_Q] the
+// block's deferred-wrap count, [BR_HIST_Q + 1] its base in the job queue
+#define BR_HIST_Q 66
+#define BR_HIST 68
+#define NO_WRAP_JOB 0xFFFFFFFFu
+
+// Extension node over key0[from..d) around the child ref `refw` (LE word
+// stream, ref_len bytes), from < d: RLP built in `ext` (>= SLOT_EXT bytes of
+// LDS), one keccak block. Result: the node's hash and its ref.
+__device__ __forceinline__ void ext_wrap(uint8_t *ext, const uint8_t *key0,
+                                         int from, int d,
+                                         const uint64_t refw[5], uint8_t ref_len,
+                                         uint64_t whash[4], uint64_t wrefw[5],
+                                         uint8_t *wrl)
+{
+    uint64_t *ext64 = (uint64_t *)ext;
+#pragma unroll
+    for (int k = 0; k < SLOT_EXT / 8; ++k)
+        ext64[k] = 0;
+    int pay = hp_item_len(from, d) + ref_len;
+    int hh = rlp_list_hdr_write(ext, pay);
+    int p = hh + hp_item_write(ext + hh, key0, from, d, 0);
+#pragma unroll
+    for (int k = 0; k < 33; ++k)
+        if (k < ref_len)
+            ext[p + k] = (uint8_t)(refw[k >> 3] >> (8 * (k & 7)));
+    int len = hh + pay; // <= 69 < SLOT_EXT
+    ext[len] = 0x01;    // pad start; end bit lands in lane 16 below
+    // single 136-B keccak block: absorb SLOT_EXT bytes + implicit zeros
+    uint64_t s[25];
+#pragma unroll
+    for (int i = 0; i < 25; ++i)
+        s[i] = 0;
+#pragma unroll
+    for (int i = 0; i < SLOT_EXT / 8; ++i)
+        s[i] ^= ext64[i];
+    s[16] ^= 0x8000000000000000ULL; // pad end bit of the 136-B block
+    keccak_f(s);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        whash[k] = s[k];
+    if (len < 32) {
+        *wrl = (uint8_t)len;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            wrefw[k] = ext64[k];
+        wrefw[4] = 0;
+    } else {
+        *wrl = 33;
+        wrefw[0] = 0xa0ull | (s[0] << 8);
+        wrefw[1] = (s[0] >> 56) | (s[1] << 8);
+        wrefw[2] = (s[1] >> 56) | (s[2] << 8);
+        wrefw[3] = (s[2] >> 56) | (s[3] << 8);
+        wrefw[4] = s[3] >> 56;
+    }
+}
+
+// Whole 48-B record composed in registers, 3 x dwordx4 stores: interval,
+// seg, parent depth P, the ref (LE word stream) and the pad byte.
+__device__ __forceinline__ void store_rec(node_rec *r, uint32_t s, uint32_t e,
+                                          uint32_t seg, int P, uint8_t rl,
+                                          const uint64_t refw[5], uint8_t pb)
+{
+    uint32_t w3 = (uint32_t)(uint8_t)(int8_t)P | ((uint32_t)rl << 8) |
+                  ((uint32_t)(refw[0] & 0xFFFF) << 16);
+    uint4 *r4 = (uint4 *)r;
+    r4[0] = make_uint4(s, e, seg, w3);
+    r4[1] = make_uint4((uint32_t)(refw[0] >> 16),
+                       (uint32_t)((refw[0] >> 48) | (refw[1] << 16)),
+                       (uint32_t)(refw[1] >> 16),
+                       (uint32_t)((refw[1] >> 48) | (refw[2] << 16)));
+    r4[2] = make_uint4((uint32_t)(refw[2] >> 16),
+                       (uint32_t)((refw[2] >> 48) | (refw[3] << 16)),
+                       (uint32_t)(refw[3] >> 16),
+                       (uint32_t)((refw[3] >> 48) & 0xFFFF) |
+                           ((uint32_t)(refw[4] & 0xFF) << 16) |
+                           ((uint32_t)pb << 24));
+}
+
+// Deferred extension wraps (plain-root mode). A hashed branch at depth d
+// under a parent junction P < d - 1 needs an extension node around it: a
+// second keccak_f that few lanes of a wave need, but which every lane's
+// issue slots pay for when it runs inside the branch kernels. With
+// `may_defer` such a lane PARKS its node instead: the final record, except
+// that the ref is still the branch's own, goes to recs[mt.s], and the lane
+// takes a rank in the block's job count (*wrap_job; NO_WRAP_JOB = not
+// parked). The kernel appends the slot to the level's job queue
+// (wrap_queue_append) and k_branch_wrap finishes the node before the level
+// ends. A parked lane leaves depths[mt.s] and the pending count of depth P
+// alone, so no select can see a half-made node; of the keccak blocks it
+// counts the branch's own, the wrap kernel adds the extension's.
+// recs[mt.s] is free for this: it is the slot the finished record goes to,
+// and no other group of the level reads it (below).
 __device__ __forceinline__ void branch_tail(
     const br_meta &mt, int subtree, const uint8_t *keys, uint64_t key_stride,
     const uint64_t br_hash[4], const uint64_t *inline_src64,
     uint64_t inline_stride, uint8_t *ext, node_rec *recs, uint8_t *depths,
     uint64_t n, uint8_t *seg_roots, uint8_t *child_refs, uint8_t *child_lens,
     uint32_t *hist_l, uint8_t *bhash_by_s, sre_update_row *urows,
-    uint32_t urowidx_val, const uint32_t *seg_by_slot)
+    uint32_t urowidx_val, const uint32_t *seg_by_slot, bool may_defer,
+    uint32_t *wrap_job)
 {
     int d = mt.d;
     int kblocks = mt.br_len / 136 + 1;
-    uint64_t *ext64 = (uint64_t *)ext;
     // branch ref as an LE word stream (bytes beyond br_ref_len are never
     // consumed: the assemble appender masks them, record stores carry them
     // deterministically)
@@ -1548,46 +1651,7 @@ __device__ __forceinline__ void branch_tail(
             wrl = br_ref_len;
             return;
         }
-#pragma unroll
-        for (int k = 0; k < SLOT_EXT / 8; ++k)
-            ext64[k] = 0;
-        int pay = hp_item_len(from, d) + br_ref_len;
-        int hh = rlp_list_hdr_write(ext, pay);
-        int p = hh + hp_item_write(ext + hh, key0, from, d, 0);
-#pragma unroll
-        for (int k = 0; k < 33; ++k)
-            if (k < br_ref_len)
-                ext[p + k] = (uint8_t)(br_refw[k >> 3] >> (8 * (k & 7)));
-        p += br_ref_len;
-        int len = hh + pay; // <= 69 < SLOT_EXT
-        ext[len] = 0x01;    // pad start; end bit lands in lane 16 below
-        // single 136-B keccak block: absorb SLOT_EXT bytes + implicit zeros
-        uint64_t s[25];
-#pragma unroll
-        for (int i = 0; i < 25; ++i)
-            s[i] = 0;
-#pragma unroll
-        for (int i = 0; i < SLOT_EXT / 8; ++i)
-            s[i] ^= ext64[i];
-        s[16] ^= 0x8000000000000000ULL; // pad end bit of the 136-B block
-        keccak_f(s);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            whash[k] = s[k];
-        if (len < 32) {
-            wrl = (uint8_t)len;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                wrefw[k] = ext64[k];
-            wrefw[4] = 0;
-        } else {
-            wrl = 33;
-            wrefw[0] = 0xa0ull | (s[0] << 8);
-            wrefw[1] = (s[0] >> 56) | (s[1] << 8);
-            wrefw[2] = (s[1] >> 56) | (s[2] << 8);
-            wrefw[3] = (s[2] >> 56) | (s[3] << 8);
-            wrefw[4] = s[3] >> 56;
-        }
+        ext_wrap(ext, key0, from, d, br_refw, br_ref_len, whash, wrefw, &wrl);
         kblocks += 1;
     };
 
@@ -1603,31 +1667,29 @@ __device__ __forceinline__ void branch_tail(
     uint8_t upd_bits = (uint8_t)(((mt.flags & 1) << 4) |
                                  ((mt.br_len >= 32 ? 1 : 0) << 5));
     if (mt.P >= 0) {
-        wrap(mt.P + 1);
-        uint8_t pb = (uint8_t)(nib_of(key0, mt.P) | upd_bits);
-        // whole 48-B record composed in registers, 3 x dwordx4 stores
-        uint32_t w3 = (uint32_t)(uint8_t)(int8_t)mt.P | ((uint32_t)wrl << 8) |
-                      ((uint32_t)(wrefw[0] & 0xFFFF) << 16);
-        if (mt.s < n) {
-            uint4 *r4 = (uint4 *)&recs[mt.s];
-            r4[0] = make_uint4(mt.s, mt.e, mt.seg, w3);
-            r4[1] = make_uint4((uint32_t)(wrefw[0] >> 16),
-                               (uint32_t)((wrefw[0] >> 48) | (wrefw[1] << 16)),
-                               (uint32_t)(wrefw[1] >> 16),
-                               (uint32_t)((wrefw[1] >> 48) | (wrefw[2] << 16)));
-            r4[2] = make_uint4((uint32_t)(wrefw[2] >> 16),
-                               (uint32_t)((wrefw[2] >> 48) | (wrefw[3] << 16)),
-                               (uint32_t)(wrefw[3] >> 16),
-                               (uint32_t)((wrefw[3] >> 48) & 0xFFFF) |
-                                   ((uint32_t)(wrefw[4] & 0xFF) << 16) |
-                                   ((uint32_t)pb << 24));
-            depths[mt.s] = (uint8_t)(mt.P + 1);
+        // child nibble at P: from the record's key word while it reaches
+        // (P < 8), else one byte of the entry's key
+        uint8_t pb = (uint8_t)((mt.P < 8 ? (mt.seg >> (28 - 4 * mt.P)) & 0xF
+                                         : nib_of(key0, mt.P)) |
+                               upd_bits);
+        if (may_defer && d > mt.P + 1 && mt.br_len >= 32 && mt.s < n) {
+            store_rec(&recs[mt.s], mt.s, mt.e, mt.seg, mt.P, br_ref_len, br_refw,
+                      pb);
+            *wrap_job = atomicAdd(&hist_l[BR_HIST_Q], 1u);
+        } else {
+            wrap(mt.P + 1);
+            if (mt.s < n) {
+                store_rec(&recs[mt.s], mt.s, mt.e, mt.seg, mt.P, wrl, wrefw, pb);
+                depths[mt.s] = (uint8_t)(mt.P + 1);
+            }
+            atomicAdd(&hist_l[mt.P + 1], 1u);
         }
-        atomicAdd(&hist_l[mt.P + 1], 1u);
     } else {
         // storage pass: records carry no segment id; a root looks its own up
-        // by its first entry (one load per segment root, off the group path)
-        const uint32_t seg = seg_by_slot ? seg_by_slot[mt.s] : mt.seg;
+        // by its first entry (one load per segment root, off the group path).
+        // Account pass: the shard (top nibble) in subtree mode, else 0
+        const uint32_t seg = seg_by_slot ? seg_by_slot[mt.s]
+                                         : (subtree ? mt.seg >> 28 : 0u);
         if (subtree) {
             wrap(1);
             uint8_t *cr = child_refs + 33ull * seg;
@@ -1641,6 +1703,36 @@ __device__ __forceinline__ void branch_tail(
         memcpy(seg_roots + 32ull * seg, whash, 32);
     }
     atomicAdd(&hist_l[65], (uint32_t)kblocks);
+}
+
+// A level's deferred-wrap jobs: the slots of the parked nodes, in no
+// particular order. jobs == nullptr: every wrap runs inline.
+struct wrap_queue {
+    uint32_t *jobs = nullptr;
+    uint32_t *count = nullptr; // device word: jobs appended so far
+    uint32_t cap = 0;
+};
+
+// Append the block's parked slots to the queue, one global atomic per block
+// (as for pending[]). Called by every thread of the block, after the
+// __syncthreads() that follows branch_tail.
+__device__ __forceinline__ void wrap_queue_append(const wrap_queue &q,
+                                                  uint32_t *hist_l,
+                                                  uint32_t wrap_job,
+                                                  uint32_t slot, uint32_t *err)
+{
+    if (!q.jobs || !hist_l[BR_HIST_Q]) // uniform over the block
+        return;
+    if (threadIdx.x == 0)
+        hist_l[BR_HIST_Q + 1] = atomicAdd(q.count, hist_l[BR_HIST_Q]);
+    __syncthreads();
+    if (wrap_job == NO_WRAP_JOB)
+        return;
+    uint32_t pos = hist_l[BR_HIST_Q + 1] + wrap_job;
+    if (pos < q.cap) // always: cap = the level's groups, one job per group
+        q.jobs[pos] = slot;
+    else
+        atomicOr(err, 1u << E_INTERNAL);
 }
 
 // Hash one branch per lane: absorb the padded slot straight from global,
@@ -1658,18 +1750,20 @@ __global__ void __launch_bounds__(BLOCK) k_branch_hash(
     sre_update_row *__restrict__ urows, /* updates mode: this level's rows */
     const uint32_t *__restrict__ urowidx,
     const uint32_t *__restrict__ seg_by_slot /* storage pass: segment id per
-                                                entry; null = mt.seg */)
+                                                entry; null = account pass */,
+    wrap_queue wq)
 {
     // pending[] updates are LDS-aggregated: one global atomic per counter
     // per block instead of per group (a single hot counter word saturates at
     // ~88 atomics/us chip-wide and was the dominant cost of this kernel).
-    __shared__ __align__(16) uint8_t lds[BLOCK * SLOT_EXT + 66 * 4];
+    __shared__ __align__(16) uint8_t lds[BLOCK * SLOT_EXT + BR_HIST * 4];
     uint32_t *hist_l = (uint32_t *)(lds + BLOCK * SLOT_EXT);
-    if (threadIdx.x < 66)
+    if (threadIdx.x < BR_HIST)
         hist_l[threadIdx.x] = 0;
     __syncthreads();
     uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = g < n_groups;
+    uint32_t wrap_job = NO_WRAP_JOB;
     br_meta mt{};
     if (active) {
         mt = meta[g]; // meta/scratch by thread slot
@@ -1701,11 +1795,13 @@ __global__ void __launch_bounds__(BLOCK) k_branch_hash(
     branch_tail(mt, subtree, keys, key_stride, br_hash, inl, inl_stride,
                 lds + (uint64_t)threadIdx.x * SLOT_EXT, recs, depths, n,
                 seg_roots, child_refs, child_lens, hist_l, bhash_by_s, urows,
-                urowidx ? urowidx[g] : 0xFFFFFFFFu, seg_by_slot);
+                urowidx ? urowidx[g] : 0xFFFFFFFFu, seg_by_slot,
+                wq.jobs != nullptr, &wrap_job);
     } // active
     __syncthreads();
     if (threadIdx.x < 66 && hist_l[threadIdx.x])
         atomicAdd(&pending[threadIdx.x], hist_l[threadIdx.x]);
+    wrap_queue_append(wq, hist_l, wrap_job, mt.s, err);
 }
 
 
@@ -1727,14 +1823,16 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
     uint8_t *__restrict__ seg_roots, uint8_t *__restrict__ child_refs,
     uint8_t *__restrict__ child_lens, uint32_t *__restrict__ pending,
     uint32_t *__restrict__ err,
-    const uint32_t *__restrict__ seg_by_slot /* as in k_branch_hash */)
+    const uint32_t *__restrict__ seg_by_slot /* as in k_branch_hash */,
+    wrap_queue wq)
 {
-    __shared__ __align__(16) uint8_t lds[BLOCK * SLOT_F1 + 66 * 4];
+    __shared__ __align__(16) uint8_t lds[BLOCK * SLOT_F1 + BR_HIST * 4];
     uint32_t *hist_l = (uint32_t *)(lds + BLOCK * SLOT_F1);
-    if (threadIdx.x < 66)
+    if (threadIdx.x < BR_HIST)
         hist_l[threadIdx.x] = 0;
     __syncthreads();
     uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t wrap_job = NO_WRAP_JOB, wrap_slot = 0;
     if (g < n_groups) {
         uint32_t gg = perm[g];
         uint64_t j = gs[gg], jend = gs[gg + 1];
@@ -1852,8 +1950,70 @@ __global__ void __launch_bounds__(BLOCK) k_branch_fused1(
             branch_tail(mt, subtree, keys, key_stride, br_hash, slot64, 1,
                         slot, recs, depths, n, seg_roots, child_refs,
                         child_lens, hist_l,
-                        nullptr, nullptr, 0xFFFFFFFFu, seg_by_slot);
+                        nullptr, nullptr, 0xFFFFFFFFu, seg_by_slot,
+                        wq.jobs != nullptr, &wrap_job);
+            wrap_slot = mt.s;
         }
+    }
+    __syncthreads();
+    if (threadIdx.x < 66 && hist_l[threadIdx.x])
+        atomicAdd(&pending[threadIdx.x], hist_l[threadIdx.x]);
+    wrap_queue_append(wq, hist_l, wrap_job, wrap_slot, err);
+}
+
+// Finish the level's parked nodes (branch_tail), one job per lane: wrap the
+// extension over key[P+1..d) around the branch ref the record holds, store
+// the finished record, and only then make the node visible to the selects
+// (depths[s], pending[P+1]). Grid-strides over the queue, whose length it
+// reads on the device. Runs after every branch kernel of the level.
+__global__ void __launch_bounds__(BLOCK) k_branch_wrap(
+    wrap_queue wq, int d, const uint8_t *__restrict__ keys, uint64_t key_stride,
+    node_rec *__restrict__ recs, uint8_t *__restrict__ depths, uint64_t n,
+    uint32_t *__restrict__ pending, uint32_t *__restrict__ err)
+{
+    __shared__ __align__(16) uint8_t lds[BLOCK * SLOT_EXT + 66 * 4];
+    uint32_t *hist_l = (uint32_t *)(lds + BLOCK * SLOT_EXT);
+    if (threadIdx.x < 66)
+        hist_l[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t cnt = *wq.count;
+    if (cnt > wq.cap) // the appender has flagged it
+        cnt = wq.cap;
+    for (uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; j < cnt;
+         j += (uint64_t)gridDim.x * BLOCK) {
+        const uint32_t s = wq.jobs[j];
+        if (s >= n) {
+            atomicOr(err, 1u << E_INTERNAL);
+            continue;
+        }
+        const uint4 *r4 = (const uint4 *)&recs[s];
+        const uint4 a = r4[0], b = r4[1], c = r4[2];
+        const int P = (int)(int8_t)(a.w & 0xFF);
+        const uint8_t rl = (uint8_t)(a.w >> 8);
+        if (P < 0 || P + 1 >= d || rl != 33 || a.x != s) { // not a parked node
+            atomicOr(err, 1u << E_INTERNAL);
+            continue;
+        }
+        // ref byte i lives at record byte 14+i: back to the LE word stream
+        uint64_t refw[5];
+        refw[0] = ((uint64_t)a.w >> 16) | ((uint64_t)b.x << 16) |
+                  ((uint64_t)b.y << 48);
+        refw[1] = ((uint64_t)b.y >> 16) | ((uint64_t)b.z << 16) |
+                  ((uint64_t)b.w << 48);
+        refw[2] = ((uint64_t)b.w >> 16) | ((uint64_t)c.x << 16) |
+                  ((uint64_t)c.y << 48);
+        refw[3] = ((uint64_t)c.y >> 16) | ((uint64_t)c.z << 16) |
+                  ((uint64_t)c.w << 48);
+        refw[4] = ((uint64_t)c.w >> 16) & 0xFF;
+        uint64_t whash[4], wrefw[5];
+        uint8_t wrl;
+        ext_wrap(lds + (uint64_t)threadIdx.x * SLOT_EXT,
+                 keys + (uint64_t)s * key_stride, P + 1, d, refw, rl, whash,
+                 wrefw, &wrl);
+        store_rec(&recs[s], a.x, a.y, a.z, P, wrl, wrefw, (uint8_t)(c.w >> 24));
+        depths[s] = (uint8_t)(P + 1);
+        atomicAdd(&hist_l[P + 1], 1u);
+        atomicAdd(&hist_l[65], 1u);
     }
     __syncthreads();
     if (threadIdx.x < 66 && hist_l[threadIdx.x])
@@ -1875,7 +2035,7 @@ __global__ void __launch_bounds__(BLOCK) k_emit_updates(
     const uint32_t *__restrict__ perm,
     uint32_t *__restrict__ rowidx /* per thread slot: row slot or ~0 */,
     const uint32_t *__restrict__ seg_by_slot /* storage pass: segment id per
-                                                entry; null = mt.seg */)
+                                                entry; null = account pass */)
 {
     __shared__ uint32_t lds[BLOCK];
     __shared__ uint32_t base;
@@ -1934,7 +2094,7 @@ __global__ void __launch_bounds__(BLOCK) k_emit_updates(
     // stash seg for the host-side acct_key patch; zero the rest
     for (int q = 0; q < 32; ++q)
         row->acct_key[q] = 0;
-    const uint32_t seg = seg_by_slot ? seg_by_slot[mt.s] : mt.seg;
+    const uint32_t seg = seg_by_slot ? seg_by_slot[mt.s] : 0u;
     memcpy(row->pad_, &seg, 4);
     row->pad_[4] = 0;
     row->removed = 0;
@@ -3050,8 +3210,7 @@ __device__ __forceinline__ uint32_t cell_of_key(const uint8_t *key)
 // members are still as the previous levels left them.
 __global__ void k_capture_L(const node_rec *__restrict__ recs,
                             const uint32_t *__restrict__ idx, uint64_t n,
-                            const uint8_t *__restrict__ keys,
-                            uint64_t key_stride, cap_row *__restrict__ out,
+                            cap_row *__restrict__ out,
                             uint32_t *__restrict__ cnt, uint64_t capacity,
                             uint32_t *__restrict__ err,
                             const uint8_t *__restrict__ bhash_by_s /* null
@@ -3076,7 +3235,7 @@ __global__ void k_capture_L(const node_rec *__restrict__ recs,
     cap_row r;
     const uint32_t s = idx[j]; // the member's slot, and its s
     copy_rec(&r.rec, &recs[s]);
-    r.cell = cell_of_key(keys + (uint64_t)s * key_stride);
+    r.cell = r.rec.seg >> 12; // cell_of_key of the record's first key
     r.pad_[0] = r.pad_[1] = r.pad_[2] = 0;
     if (bhash_by_s)
         memcpy(r.bhash, bhash_by_s + 32ull * s, 32);
@@ -3895,10 +4054,10 @@ struct level_in {
     const uint32_t *hist_host = nullptr; // records per depth bucket [66]
     int subtree = 0;
     uint8_t *seg_roots = nullptr, *child_refs = nullptr, *child_lens = nullptr;
-    // storage pass: segment id per entry. Its records carry seg = 0 (the ids
-    // are scanned after the leaf kernel) and the id is read as
+    // storage pass: segment id per entry. Records carry the key word, not an
+    // id (the ids are scanned after the leaf kernel); the id is read as
     // seg_by_slot[s] where it is consumed. Null in the account pass, whose
-    // records carry seg themselves.
+    // shard is the key word's top nibble.
     const uint32_t *seg_by_slot = nullptr;
     uint32_t *err = nullptr;
     // -1 = off; 0/1 = retain TrieUpdates rows of this trie kind (bhash then
@@ -3958,9 +4117,11 @@ struct level_work {
     uint64_t chunk = 0; // branch-pipeline chunk, in groups
     bool use_cls = false, use_fused = false, pipe2 = false;
     DBuf perm, ccnt, coff, scratch2, meta2, cinv;
+    DBuf wq_jobs, wq_count; // deferred extension wraps (wrap_queue)
     std::vector<uint32_t> c0s; // per chunk: class-0 group count (fused)
     explicit level_work(sre_ctx *c)
-        : perm(c), ccnt(c), coff(c), scratch2(c), meta2(c), cinv(c)
+        : perm(c), ccnt(c), coff(c), scratch2(c), meta2(c), cinv(c),
+          wq_jobs(c), wq_count(c)
     {
     }
 };
@@ -4083,6 +4244,26 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
     Event ev_asm[2] = {Event(hipEventDisableTiming), Event(hipEventDisableTiming)};
     Event ev_hash[2] = {Event(hipEventDisableTiming),
                         Event(hipEventDisableTiming)};
+    // Plain-root calls defer the extension wraps of hashed non-root branches
+    // to one k_branch_wrap at the end of the level (branch_tail). A wrap
+    // needs d > P + 1 >= 1, so levels 0 and 1 have none. Only levels wide
+    // enough for the class partition defer: below that gate a level is a
+    // few waves, and the queue's memset and launch cost more than the
+    // keccak_f they save (with the queue on every level the storage-bearing
+    // incremental workload measured +0.15 ms per step). Updates
+    // and proof calls keep every wrap inline; SRE_NO_DEFER_WRAP=1 forces
+    // that (test gate, read per call). One job per group at most: 4 B per
+    // group.
+    wrap_queue wq;
+    if (d >= 2 && w.use_cls && !updates && proof.n == 0 &&
+        getenv("SRE_NO_DEFER_WRAP") == nullptr) {
+        HIP_CHECK(ctx, w.wq_jobs.alloc((uint64_t)w.n_groups * 4));
+        HIP_CHECK(ctx, w.wq_count.alloc(4));
+        HIP_CHECK(ctx, hipMemsetAsync(w.wq_count.p, 0, 4, ctx->stream));
+        wq.jobs = w.wq_jobs.as<uint32_t>();
+        wq.count = w.wq_count.as<uint32_t>();
+        wq.cap = w.n_groups;
+    }
     // stream2 must not outrun state main-stream work this level depends
     // on (idx, gs, perm are ready once the partition above completes)
     HIP_CHECK(ctx, hipEventRecord(ev_hash[0].ev, ctx->stream));
@@ -4126,13 +4307,15 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
                    gs + g0, c0m, in.lcp, in.keys, in.key_stride, d, in.subtree,
                    in.recs, in.depths, in.n, w.perm.as<uint32_t>() + g0,
                    in.seg_roots,
-                   in.child_refs, in.child_lens, pend, in.err, in.seg_by_slot);
+                   in.child_refs, in.child_lens, pend, in.err, in.seg_by_slot,
+                   wq);
         if (c0t)
             LAUNCH(ctx, k_branch_fused1, grid_for(c0t), BLOCK, s_asm, w.idx,
                    gs + g0, c0t, in.lcp, in.keys, in.key_stride, d, in.subtree,
                    in.recs, in.depths, in.n,
                    w.perm.as<uint32_t>() + g0 + c0m, in.seg_roots,
-                   in.child_refs, in.child_lens, pend, in.err, in.seg_by_slot);
+                   in.child_refs, in.child_lens, pend, in.err, in.seg_by_slot,
+                   wq);
         if (pipe2)
             HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ev_asm[buf].ev, 0));
         if (proof.n) // multiproof: copy path-node RLPs out of scratch
@@ -4158,7 +4341,7 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
                    in.child_lens, pend, in.err, in.bhash,
                    updates ? bufs.urows.as<sre_update_row>() : nullptr,
                    updates ? bufs.urowidx.as<uint32_t>() : nullptr,
-                   in.seg_by_slot);
+                   in.seg_by_slot, wq);
         if (pipe2)
             HIP_CHECK(ctx, hipEventRecord(ev_hash[buf].ev, ctx->stream));
         if (updates) {
@@ -4179,6 +4362,12 @@ static int run_branch_chunks(sre_ctx *ctx, const level_in &in,
                  // level's outputs are consumed
         HIP_CHECK(ctx, hipEventRecord(ev_asm[0].ev, ctx->stream2));
         HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ev_asm[0].ev, 0));
+    }
+    if (wq.jobs && w.n_groups) { // every producer of the queue is ordered before this
+        const uint32_t grid = grid_for(w.n_groups);
+        LAUNCH(ctx, k_branch_wrap, grid < 2048 ? grid : 2048, BLOCK, ctx->stream,
+               wq, d, in.keys, in.key_stride, in.recs, in.depths, in.n, pend,
+               in.err);
     }
     HIP_CHECK(ctx, timer.stop(ctx->stream));
     return 0;
@@ -4221,7 +4410,7 @@ static int run_levels(sre_ctx *ctx, const level_in &in, pass_out *po,
             return -1;
         if (cap.depth > 0 && d == cap.depth - 1)
             LAUNCH(ctx, k_capture_L, grid_for(w.n_level), BLOCK, ctx->stream,
-                   in.recs, w.idx, w.n_level, in.keys, in.key_stride, cap.rows, cap.count,
+                   in.recs, w.idx, w.n_level, cap.rows, cap.count,
                    cap.capacity, in.err,
                    in.updates_kind >= 0 ? in.bhash : nullptr);
         if (partition_classes(ctx, in, proof.n, bufs, w) ||
